@@ -1,7 +1,13 @@
 #!/usr/bin/env python3
 """Headline benchmark: env-steps/sec at 65 536 concurrent DemoMap games per MI355X, random vs random.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--envs E]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--envs E] [--dump-outputs DIR] [--full]
+
+A plain run sets up, warms up, times exactly K steps in one region and prints the headline line (`value`, `ms_per_step` = the
+wall clock of that region / K); --dump-outputs DIR also writes what the last timed step returned (obs, reward, done, winner,
+scores, status, orders) as DIR/<name>.npy.  --full adds everything below that is not the headline: the cold region, the
+median of R regions, the sustained leg, the per-turn / float64 / pipelined legs, the roofline objects, the CPU baseline and
+the CPU replay of the measured games.
 
 One "step" = one pass of the hot path over one batch: on-device random action generation for both
 players of every env (the input generator, agents/State_Machine/random_actions.py) + the fused
@@ -23,7 +29,7 @@ So that the timed regions measure the rollout rate and not the governor's ramp, 
 rollouts for --clock-warmup-ms (default 80) right before the W warm-up steps; the line reports it (timing.clock_warmup_ms), and
 --clock-warmup-ms 0 gives the cold figure.
 
-Besides the headline (persistent rollout form) the line carries, under config, three legs that pay one step launch per turn --
+With --full, besides the headline (persistent rollout form) the line carries, under config, three legs that pay one step launch per turn --
 what a Gym consumer gets from env.step(): `one_launch_per_turn` (orders drawn inside the step kernel),
 `caller_actions_per_turn` (per turn evg_random_actions into a caller tensor, then evg_step(actions): the reference's
 loop evaluate.py:143-152 with both policies' output arriving in a tensor) and `learner_vs_bot_per_turn` (the loop the
@@ -32,8 +38,8 @@ evg_random_actions_seat --, an on-device bot on seat 1 evaluated INSIDE the step
 written: evg_step_vs_policy) -- each with its own roofline object.
 
 The stdout line is the COMPACT form of the result (every number, ~3 KB: a driver that keeps only the tail of the output must
-still see one whole JSON object); `--details FILE` also writes the full object with its explanatory strings (~8 KB), which is
-what tools/bench_set.sh commits under profiles/.
+still see one whole JSON object); `--details FILE` also writes the full object with its explanatory strings (~8 KB; with --full),
+which is what tools/bench_set.sh commits under profiles/.
 
 For N > 1 the driver launches one rank per GPU (torch.distributed.run); environments shard by
 contiguous global id (weak scaling: 65 536 per GPU) and the only collective is the gather of episode
@@ -69,6 +75,7 @@ VALU_PEAK_WAVE_INSTS_PER_S = 256 * 4 * 2.4e9 / 4.0   # 1024 SIMDs x 2.4 GHz / 4 
 REFERENCE_PYTHON_ENV_STEPS_PER_S = (529, 554)   # the reference's own Python turn loop on ONE core (measured in the build container)
 NOMINAL_MS_PER_STEP = 0.02   # for the repeat rule of the timed region only (one rule for every rank, box and batch size)
 PHASES = 150                 # episode length of random vs random (server.py:321): the pre-roll spreads phases over it
+DUMP_BUDGET_BYTES = 48 * 10 ** 6   # --dump-outputs: at most this much in all (a seeded sample of env rows above it)
 
 
 def usable_cores():
@@ -225,10 +232,27 @@ def expected_if_wire_free(world, steps):
     return out
 
 
-def repeats_for(steps, forced=0):
-    """How often the exact K-step region is timed: `forced` when given, else 9 when K x a nominal 0.02 ms < 50 ms (K <= 2 500) and 1 otherwise.  The rule
-    depends on nothing a rank measures, so every rank of a multi-GPU job times the same number of regions."""
-    return forced if forced > 0 else (9 if steps * NOMINAL_MS_PER_STEP < 50.0 else 1)
+def repeats_for(steps, forced=0, full=True):
+    """How often the exact K-step region is timed: `forced` when given; else 1 in a plain run, and with --full 9 when K x a nominal 0.02 ms < 50 ms
+    (K <= 2 500) and 1 otherwise.  The rule depends on nothing a rank measures, so every rank of a multi-GPU job times the same number of regions."""
+    return forced if forced > 0 else (9 if full and steps * NOMINAL_MS_PER_STEP < 50.0 else 1)
+
+
+def dump_outputs(directory, arrays, seed):
+    """--dump-outputs: {name: host array with the env rows first} -> directory/<name>.npy (float32; float64 stays float64).  When the rows take more than
+    DUMP_BUDGET_BYTES, a fixed sample of rows drawn with `seed` (sorted) is written instead, and its row indices as env_index.npy."""
+    import numpy as np
+    os.makedirs(directory, exist_ok=True)
+    arrays = {k: np.ascontiguousarray(v, dtype=np.float64 if v.dtype == np.float64 else np.float32) for k, v in arrays.items()}
+    n = len(next(iter(arrays.values())))
+    per_row = sum(v.nbytes for v in arrays.values()) / n
+    if per_row * n > DUMP_BUDGET_BYTES:
+        rows = np.sort(np.random.default_rng(seed).choice(n, int(DUMP_BUDGET_BYTES // (per_row + 8)), replace=False))
+        arrays = {k: v[rows] for k, v in arrays.items()}
+        arrays["env_index"] = rows.astype(np.float64)
+    for k, v in arrays.items():
+        np.save(os.path.join(directory, k + ".npy"), v)
+    return sorted(arrays)
 
 
 def median_regions(region_s):
@@ -313,13 +337,11 @@ def compact_line(full):
                      **{k: c[k] for k in ("envs_per_gpu", "total_envs", "turns_per_launch", "launch_form", "parallelism", "kernel_source_hash",
                                           "episodes_finished_rank0",
                                           "wins_p0_p1_tie_rank0", "gathered_wins_all_ranks") if k in c},
-                     "one_launch_per_turn": leg(c.get("one_launch_per_turn")), "caller_actions_per_turn": leg(c.get("caller_actions_per_turn")),
-                     "learner_vs_bot_per_turn": leg(c.get("learner_vs_bot_per_turn")),
-                     "learner_smart_actions_vs_bot_per_turn": leg(c.get("learner_smart_actions_vs_bot_per_turn")),
-                     "pipelined_halves_per_turn": leg(c.get("pipelined_halves_per_turn")),
-                     "obs_float64": leg(c.get("obs_float64")),
-                     "without_observations": leg(c.get("without_observations"))}
-    out["roofline"] = roof(full["roofline"])
+                     **{k: leg(c.get(k)) for k in ("one_launch_per_turn", "caller_actions_per_turn", "learner_vs_bot_per_turn",
+                                                   "learner_smart_actions_vs_bot_per_turn", "pipelined_halves_per_turn", "obs_float64", "without_observations")
+                        if k in c}}
+    if "roofline" in full:
+        out["roofline"] = roof(full["roofline"])
     if "timing" in full:
         t = full["timing"]
         out["timing"] = {"repeats": t["repeats"], "reported": t["reported"], "min_ms_per_step": _r(t["min_ms_per_step"], 5),
@@ -559,9 +581,17 @@ def parse_args(argv=None):
     ap.add_argument("--collective", default="torch", choices=["torch", "evg"],
                     help="N > 1: the gather of episode results through torch.distributed (default; backend nccl = RCCL) or through the library's own RCCL entry "
                          "points (evg_comm_init / evg_gather_returns: pack kernel + grouped send / receive on the launches' stream, no framework stream hop)")
+    ap.add_argument("--full", action="store_true",
+                    help="everything besides the headline: the cold region, the median of R regions, the sustained leg, the per-turn / float64 / pipelined "
+                         "legs, the roofline objects, the CPU baseline and the CPU replay of the measured games (and for N > 1 the distributed block).  "
+                         "Without it a run sets up, warms up, times exactly --steps steps in ONE region and prints the headline line")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="after the timed steps, write what the timed path returned for its last step (obs, reward, done, winner, scores, status and the "
+                         "orders of that turn; rank 0's envs) as DIR/<name>.npy in float32 (float64 observations stay float64); above %d MB a fixed sample "
+                         "of env rows seeded by --seed, listed in DIR/env_index.npy" % (DUMP_BUDGET_BYTES // 10 ** 6))
     ap.add_argument("--repeats", type=int, default=0,
-                    help="how often the exact K-step region is timed (value = the median region); 0 = auto: 9 when K x a nominal 0.02 ms < 50 ms (K <= 2500), "
-                         "else 1")
+                    help="how often the exact K-step region is timed (value = the median region); 0 = auto: 1, with --full 9 when K x a nominal 0.02 ms "
+                         "< 50 ms (K <= 2500), else 1")
     ap.add_argument("--clock-warmup-ms", type=float, default=80.0,
                     help="untimed: a SCRATCH handle of the same size plays rollouts for this long right before the --warmup steps, so that the timed regions run at "
                          "the shader clock a long rollout sustains (the governor needs 30-40 ms of load to get there: "
@@ -643,9 +673,11 @@ class Run(object):
             whole loop of single-turn launches)."""
             if fused == "learner":        # per turn: evg_random_actions_seat -> tensor [N,7,2] -> evg_step_vs_policy (bot inside the step kernel)
                 out = env.rollout_vs(nsteps, args.opponent, seat=0, time_kernel=timed)
+                rollout.last = (out[:4], env._actions_seat)
                 return out[-1] * nsteps if timed else 0.0
             kw = dict(time_kernel=timed, fused=fused, turns_per_launch=tpl, observe=observe, record_actions=observe, prepare=prepare)
             out = (env.rollout_random(nsteps, **kw) if args.workload == "random" else env.rollout_policies(nsteps, "cycle_rush_turn25", "swarm", **kw))
+            rollout.last = (out[:4], env._actions)        # what the caller of the last call holds: (obs, reward, done, info) and the orders of the turn
             return out[-1] * nsteps if timed else 0.0
 
         desynchronise(env, self.first, args.workload, rollout)
@@ -696,12 +728,12 @@ class Run(object):
         with GRBM_GUI_ACTIVE in profiles/r05_d_default_run_kernel_stats.csv) -- so a region timed 10 ms after the start of the process (the driver's --steps 20
         --warmup 5) measures the governor's ramp, 14 % below what every later millisecond of a rollout gets.  A scratch handle of the same size plays 150-turn
         rollouts for --clock-warmup-ms right before the W warm-up steps; the measured handle, its games and the W / K contract are untouched.  So that the
-        line shows what this is worth, ONE K-step region is timed BEFORE it with the clock the process has at that moment (what rounds 1-4 reported as the
-        value): same brackets, same launches, reported as `value_cold` next to `value`."""
+        --full line shows what this is worth, ONE K-step region is timed BEFORE it with the clock the process has at that moment (what rounds 1-4 reported as
+        the value): same brackets, same launches, reported as `value_cold` next to `value`."""
         args, torch = self.args, self.torch
         cw = {"requested_ms": args.clock_warmup_ms, "ms": 0.0, "turns": 0}
         self.scratch = None
-        if args.clock_warmup_ms > 0 and not self.dist_on and args.steps <= 2500:
+        if args.full and args.clock_warmup_ms > 0 and not self.dist_on and args.steps <= 2500:
             cold_s = self.time_one_region(args.steps, args.turns_per_launch)
             cw["cold_region"] = {"ms_per_step": cold_s / args.steps * 1e3, "value": self.total * args.steps / cold_s}
         if args.clock_warmup_ms > 0:
@@ -721,18 +753,27 @@ class Run(object):
         return cw
 
     def timed_regions(self):
-        """W untimed warm-up steps, then the exact K-step region R times.  A region of a few hundred microseconds (the driver's --steps 20: 0.4 ms) is ONE draw
-        from a distribution whose box-to-box and run-to-run spread is +-8 %: when K x a nominal 20 us per step is below 50 ms the region is repeated R = 9
-        times -- each repeat bracketed exactly like the single region (barrier + synchronize on both sides, nothing else inside) -- and value / ms_per_step come
-        from the MEDIAN region; min and max are reported next to it.  (The rule must give the SAME answer on every rank -- a rank that timed one region more
+        """W untimed warm-up steps, then the exact K-step region R times (a plain run: once).  A region of a few hundred microseconds (--steps 20: 0.4 ms)
+        is ONE draw from a distribution whose box-to-box and run-to-run spread is +-8 %: with --full, when K x a nominal 20 us per step is below 50 ms the
+        region is repeated R = 9 times -- each repeat bracketed exactly like the single region (barrier + synchronize on both sides, nothing else inside) --
+        and value / ms_per_step come from the MEDIAN region; min and max are reported next to it.  (The rule must give the SAME answer on every rank -- a rank that timed one region more
         would wait in a barrier nobody else enters -- so it uses a nominal 20 us per step, not this rank's own measurement.)
         Returns (per-region wall seconds [max over ranks], per-region kernel ms of THIS rank, per-region collective ms or None, all-ranks tensor or None)."""
         args, torch, dist = self.args, self.torch, self.dist
         if args.warmup > 0:
             self.rollout(args.warmup, True, args.turns_per_launch, self.main_fused)
             self.played += args.warmup
-        repeats = repeats_for(args.steps, args.repeats)
+        repeats = repeats_for(args.steps, args.repeats, args.full)
         use_events = self.dist_on or args.timing == "torch"
+        if not args.full and repeats == 1 and args.steps * NOMINAL_MS_PER_STEP < 50.0:
+            # the first short regions after the clock warm-up are slower until the measured handle has played about an episode length again and the K-step
+            # launch shape has run once (--steps 20 --warmup 5, us per step of consecutive regions: 21.2, 18.1, 16.4, 16.2, ...; the median of R regions
+            # leaves them out): a single short region is timed after untimed passes of the same call -- two, and at least PHASES turns --, each closed by
+            # the region's bracket like the repeats of --full are
+            for _ in range(max(2, -(-PHASES // args.steps))):
+                self.rollout(args.steps, not self.dist_on and args.timing == "native", args.turns_per_launch, self.main_fused)
+                self.played += args.steps
+                self.barrier()
         if use_events:      # torch creates an event at its first record(): not inside the timed region
             evs = [[torch.cuda.Event(enable_timing=True) for _ in range(3)] for _ in range(repeats)]
             for tri in evs:
@@ -789,7 +830,7 @@ class Run(object):
 
     def sustained_turns(self):
         a = self.args
-        return 0 if (a.sustained_launches <= 0 or self.dist_on or self.main_fused is not True or a.turns_per_launch < 2) else a.sustained_launches * PHASES
+        return 0 if (not a.full or a.sustained_launches <= 0 or self.dist_on or self.main_fused is not True or a.turns_per_launch < 2) else a.sustained_launches * PHASES
 
     def sustained_leg(self):
         """`sustained`: --sustained-launches (3) launches of 150 turns between the SAME brackets as a timed region (barrier + synchronize on both sides, the
@@ -827,6 +868,40 @@ class Run(object):
             self.gathered = self.gather(self.env.packed_episode_results())
         self.played_at_snapshot = self.played
         self.final_state = self.env.get_state() if (self.world == 1 and not args.no_cpu_baseline and args.workload == "random" and self.played <= 6000) else None
+
+    def last_step_outputs(self):
+        """--dump-outputs: host copies of what the last timed rollout call returned to its caller (the outputs of the last timed turn), env rows first"""
+        (obs, reward, done, info), orders = self.rollout.last
+        self.torch.cuda.synchronize(self.device)
+        out = {"obs": obs, "reward": reward, "done": done, "winner": info["winner"], "scores": info["scores"], "status": info["status"], "orders": orders}
+        return {k: v.cpu().numpy() for k, v in out.items()}
+
+    def headline(self, summary, cw):
+        """rank 0: the fields of the contract and what the headline was measured on -- the whole line of a plain run, the top of the --full object"""
+        args, dt = self.args, summary["seconds"]
+        timing = dict(summary["timing"], clock_warmup=cw)
+        return {
+            "metric": "env-steps/sec at 65536 concurrent DemoMap games, 1/2/4/8 MI355X",
+            "value": self.total * args.steps / dt, "unit": "env-steps/s", "n_gpus": self.world, "steps": args.steps, "warmup": args.warmup,
+            "ms_per_step": dt / args.steps * 1e3, "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
+            "dtype": "int32+f64", "data": "synthetic",
+            "value_protocol": ("%s of exactly K steps after %g ms of untimed clock warm-up on a scratch handle"
+                               % ("one region" if timing["repeats"] == 1 else "median of %d regions" % timing["repeats"], cw["ms"])),
+            "config": {"workload": ("%d concurrent DemoMap games per GPU, random_actions vs random_actions drawn on device (fused into the step kernel, orders "
+                                    "written to an [N,2,7,2] tensor; persistent rollout form, see turns_per_launch), auto-reset, obs %s [N,2,105]"
+                                    if args.workload == "random" else
+                                    "%d concurrent DemoMap games per GPU, on-device Cycle_BRush_Turn25 vs SwarmAgent (BASELINE config 5; both bots fused into the "
+                                    "step kernel, orders written out; episodes end by BaseCapture after 84-94 turns), auto-reset, obs %s [N,2,105]")
+                                   % (self.n_local, args.obs_dtype),
+                       "window": "desynchronised steady state: 150-turn pre-roll restarts env e at pre-roll turn hash(e) mod 150 (episode phases uniform over "
+                                 "0..149, unrelated between neighbouring envs), then 150 settle turns, --warmup turns and the K timed turns",
+                       "envs_per_gpu": self.n_local, "total_envs": self.total, "turns_per_launch": args.turns_per_launch,
+                       "turns_of_last_timed_launch": args.steps % args.turns_per_launch or min(args.turns_per_launch, args.steps),
+                       "launch_form": "persistent" if args.turns_per_launch > 1 else ("caller_actions_per_turn" if args.caller_actions else (
+                           "learner_vs_bot_per_turn" if args.learner_seat else "one_launch_per_turn")),
+                       "parallelism": "env-sharded x%d" % self.world},
+            "timing": timing,
+        }
 
     # ------------------------------------------------------------------------------------------------------------------------------------------------
     def per_turn_leg(self, fused):
@@ -1073,38 +1148,24 @@ class Run(object):
 
     def report(self, summary, cw, sustained, legs, dist_block):
         """rank 0: the full result object"""
-        args, env, evg = self.args, self.env, self.evg
-        dt, steps = summary["seconds"], args.steps
-        tpl = args.turns_per_launch
-        step_kernel_ms = summary["kernel_ms_sum"] / steps
-        ms_per_step = dt / steps * 1e3
-        roof, valu, main_form = self.price_roofline(step_kernel_ms, ms_per_step, legs)
+        args, evg = self.args, self.evg
+        head = self.headline(summary, cw)
+        roof, valu, _ = self.price_roofline(summary["kernel_ms_sum"] / args.steps, head["ms_per_step"], legs)
         st = self.stats
-        timing = dict(summary["timing"], clock_warmup=cw)
         cold = (cw.get("cold_region") or {}).get("value")
+        timing = head["timing"]
         out = {
-            "metric": "env-steps/sec at 65536 concurrent DemoMap games, 1/2/4/8 MI355X",
-            "value": self.total * steps / dt, "unit": "env-steps/s", "n_gpus": self.world, "steps": steps, "warmup": args.warmup,
-            "ms_per_step": ms_per_step, "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
-            "dtype": "int32+f64", "data": "synthetic",
+            **{k: head[k] for k in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling", "vs_baseline",
+                                    "dtype", "data")},
             # what rounds 1-4 reported as `value`: ONE K-step region timed before the clock warm-up, same brackets (None: --clock-warmup-ms 0 or N > 1)
             "value_cold": cold,
             "value_protocol": ("median of %d regions of exactly K steps after %g ms of untimed clock warm-up on a scratch handle (round 5 on); value_cold = one "
                                "region before it (the protocol of rounds 1-4); sustained = %d x 150-turn launches in one region"
                                % (timing["repeats"], cw["ms"], args.sustained_launches)),
             "sustained": sustained,
-            "config": dict({"workload": ("%d concurrent DemoMap games per GPU, random_actions vs random_actions drawn on device (fused into the step kernel, orders "
-                                         "written to an [N,2,7,2] tensor; persistent rollout form, see turns_per_launch), auto-reset, obs %s [N,2,105]"
-                                         if args.workload == "random" else
-                                         "%d concurrent DemoMap games per GPU, on-device Cycle_BRush_Turn25 vs SwarmAgent (BASELINE config 5; both bots fused into the "
-                                         "step kernel, orders written out; episodes end by BaseCapture after 84-94 turns), auto-reset, obs %s [N,2,105]")
-                                        % (self.n_local, args.obs_dtype),
-                            "window": "desynchronised steady state: 150-turn pre-roll restarts env e at pre-roll turn hash(e) mod 150 (episode phases uniform over "
-                                      "0..149, unrelated between neighbouring envs), then 150 settle turns, --warmup turns and the K timed turns",
-                            "envs_per_gpu": self.n_local, "total_envs": self.total, "turns_per_launch": tpl,
-                            "turns_of_last_timed_launch": steps % tpl or min(tpl, steps), "launch_form": main_form},
+            "config": dict({k: v for k, v in head["config"].items() if k != "parallelism"},
                            **legs,
-                           **{"parallelism": "env-sharded x%d" % self.world, "kernel_source_hash": kernel_source_hash(),
+                           **{"parallelism": head["config"]["parallelism"], "kernel_source_hash": kernel_source_hash(),
                               "episodes_finished_rank0": int(st["totals"][0]), "wins_p0_p1_tie_rank0": [int(x) for x in st["totals"][1:]],
                               "gathered_wins_all_ranks": list(evg.ResultGather.win_counts(self.gathered)) if self.gathered is not None else None}),
             "roofline": roof,
@@ -1138,7 +1199,26 @@ def main(argv=None):
     run.setup()
     cw = run.warm_the_clock()
     region_s, kernel_ms, collective_ms, allr = run.timed_regions()
+    if args.dump_outputs and run.rank == 0:
+        dump_outputs(args.dump_outputs, run.last_step_outputs(), args.seed)
     summary = summarise_regions(region_s, kernel_ms, collective_ms, args.steps, run.total)
+    if not args.full:
+        # a plain run: the headline only (everything else the benchmark measures or checks is behind --full)
+        if run.scratch is not None:
+            run.scratch.close()
+        if run.env.check_fault():                           # (never expected: a chunk hand-over fault of a launch plan)
+            raise SystemExit("fault")
+        if run.rank == 0:
+            out = run.headline(summary, cw)
+            if args.details:
+                with open(args.details, "w") as f:
+                    f.write(json.dumps(out) + "\n")
+            print(json.dumps(compact_line(out), separators=(",", ":")), flush=True)
+        run.env.close()
+        if run.dist_on:
+            run.dist.barrier()
+            run.dist.destroy_process_group()
+        return
     sustained = run.sustained_leg()
     if run.scratch is not None:
         run.scratch.close()

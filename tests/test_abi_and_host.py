@@ -303,6 +303,29 @@ def test_bench_times_the_region_several_times_and_reports_the_median():
     assert s["median_indices"] == [2] and s["seconds"] == 0.2 and s["kernel_ms_sum"] == 2.0 and s["collective_ms"] == 0.02
 
 
+def test_bench_plain_run_times_k_steps_once_and_dumps_its_outputs(tmp_path):
+    """A plain bench run times exactly --steps steps in ONE region (--full keeps the median-of-R rule); --dump-outputs writes every output as float32
+    (float64 stays float64), all rows while they fit the budget, else the same seeded, sorted sample of rows with its indices."""
+    bench = _load_bench("evg_bench_plain")
+    a = bench.parse_args(["--steps", "20"])
+    assert not a.full and a.dump_outputs == "" and bench.repeats_for(a.steps, a.repeats, a.full) == 1
+    assert bench.repeats_for(20, 0, full=True) == 9 and bench.repeats_for(20, 3, full=False) == 3 and bench.parse_args(["--full"]).full
+    rng = np.random.default_rng(0)
+    small = {"obs": rng.standard_normal((64, 2, 105)).astype(np.float32), "done": rng.integers(0, 2, 64).astype(np.uint8),
+             "health": rng.standard_normal((64, 2))}
+    assert bench.dump_outputs(str(tmp_path / "a"), small, 7) == ["done", "health", "obs"]
+    got = {k: np.load(str(tmp_path / "a" / (k + ".npy"))) for k in small}
+    assert got["obs"].dtype == np.float32 and got["done"].dtype == np.float32 and got["health"].dtype == np.float64
+    assert all(np.array_equal(got[k], small[k]) for k in small)
+    big = {"obs": np.arange(70000 * 210, dtype=np.float32).reshape(70000, 210), "scores": np.arange(70000 * 2, dtype=np.int32).reshape(70000, 2)}
+    for d in ("b", "c"):
+        assert bench.dump_outputs(str(tmp_path / d), big, 7) == ["env_index", "obs", "scores"]
+    rows = np.load(str(tmp_path / "b" / "env_index.npy"))
+    assert np.array_equal(rows, np.load(str(tmp_path / "c" / "env_index.npy"))) and np.all(np.diff(rows) > 0)
+    assert np.array_equal(np.load(str(tmp_path / "b" / "obs.npy")), big["obs"][rows.astype(np.int64)])
+    assert sum(os.path.getsize(str(tmp_path / "b" / f)) for f in os.listdir(str(tmp_path / "b"))) <= bench.DUMP_BUDGET_BYTES + 4096
+
+
 def test_bench_stdout_line_is_compact_and_complete():
     """bench.py prints the COMPACT form of its result: a driver that keeps only the tail of the output must still see one whole JSON
     object.  Every full line committed under profiles/ for this round compacts to less than 3.6 KB (the size of a line a driver is known

@@ -6,6 +6,7 @@
 cd "$(dirname "$0")/.."
 mkdir -p gpurun_out
 LIBS=${LIBS:-"libevg_base.so libevg.so"}
+set -- --full "$@"      # the lines are read for roofline.kernel_ms (and the per-turn leg / the R regions): fields of bench.py --full
 : > gpurun_out/ab.txt
 for rep in ${REPS:-1 2 3}; do
   for lib in $LIBS; do

@@ -8,14 +8,14 @@ cd "$(dirname "$0")/.."
 mkdir -p gpurun_out
 # stdout = the compact line the driver sees; --details = the full object (what is committed under profiles/)
 run() { name=$1; shift; timeout -k 10 400 python bench.py --details gpurun_out/bench_${TAG}_$name.full.json "$@" > gpurun_out/bench_${TAG}_$name.json 2> gpurun_out/bench_${TAG}_$name.err || { tail -5 gpurun_out/bench_${TAG}_$name.err; exit 1; }; }
-run final
-run driver_shape --steps 20 --warmup 5
-run config5 --workload scripted --no-cpu-baseline
-run 4096envs --envs 4096 --no-cpu-baseline
-run int16 --obs-dtype int16 --no-cpu-baseline
+run final --full
+run driver_shape --full --steps 20 --warmup 5
+run config5 --full --workload scripted --no-cpu-baseline
+run 4096envs --full --envs 4096 --no-cpu-baseline
+run int16 --full --obs-dtype int16 --no-cpu-baseline
 # the N > 1 code path, rehearsed on the one GPU of the box: two ranks over gloo (two processes sharing the card), and RCCL with a one-rank group
-run rehearse_gloo2 --gpus 2 --backend gloo --steps 20 --warmup 5 --no-cpu-baseline
-run rehearse_rccl1 --rehearse-distributed --steps 20 --warmup 5 --no-cpu-baseline
+run rehearse_gloo2 --full --gpus 2 --backend gloo --steps 20 --warmup 5 --no-cpu-baseline
+run rehearse_rccl1 --full --rehearse-distributed --steps 20 --warmup 5 --no-cpu-baseline
 python - <<P
 import json, glob
 for f in sorted(x for x in glob.glob("gpurun_out/bench_${TAG}_*.json") if not x.endswith(".full.json")):

@@ -10,7 +10,7 @@ R=$GRAFT_REPO_ROOT
 OUT=$R/gpurun_out/prof_${NAME}_default
 mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp
-CMD="python3 $R/bench.py --no-cpu-baseline --no-extra-legs"
+CMD="python3 $R/bench.py --full --no-cpu-baseline --no-extra-legs"
 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/stats -- $CMD > $OUT/bench.json 2> $OUT/err.txt || { tail -5 $OUT/err.txt; exit 1; }
 rocprofv3 --kernel-trace --pmc GRBM_GUI_ACTIVE --output-format csv -d $OUT/clock -- $CMD > $OUT/bench_clock.json 2> $OUT/err_clock.txt || { tail -5 $OUT/err_clock.txt; exit 1; }
 cd $R
@@ -34,7 +34,7 @@ for r in sorted((r for r in csv.DictReader(open(f)) if KERNEL in r["Kernel_Name"
     ns = int(r["End_Timestamp"]) - int(r["Start_Timestamp"])
     clk.append((ns, float(r["Counter_Value"]) / 8 / ns))
 stats = open(glob.glob("$OUT/stats/*/*_kernel_stats.csv")[0]).read().splitlines()
-out = ['"# rocprofv3 --kernel-trace --stats --output-format csv -- python3 bench.py --no-cpu-baseline --no-extra-legs      (kernel_source_hash %s)"' % line["config"]["kernel_source_hash"],
+out = ['"# rocprofv3 --kernel-trace --stats --output-format csv -- python3 bench.py --full --no-cpu-baseline --no-extra-legs      (kernel_source_hash %s)"' % line["config"]["kernel_source_hash"],
        '"# persistent step-kernel dispatches of the run, in order (us): %s"' % " ".join("%.0f" % (d / 1e3) for d in durs),
        '"# the LAST %d dispatches are the sustained leg (one region): %s us; the line says sustained.kernel_ms = %s, sustained.ms_per_step = %s"'
        % (S, " ".join("%.0f" % (x / 1e3) for x in sust), (line.get("sustained") or {}).get("kernel_ms"), (line.get("sustained") or {}).get("ms_per_step")),

@@ -7,7 +7,7 @@ R=$GRAFT_REPO_ROOT
 OUT=$R/gpurun_out/prof_${NAME}_driver
 mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp
-rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/stats -- python3 $R/bench.py --gpus 1 --steps 20 --warmup 5 --no-cpu-baseline --no-extra-legs > $OUT/bench.json 2> $OUT/err.txt || { tail -5 $OUT/err.txt; exit 1; }
+rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/stats -- python3 $R/bench.py --full --gpus 1 --steps 20 --warmup 5 --no-cpu-baseline --no-extra-legs > $OUT/bench.json 2> $OUT/err.txt || { tail -5 $OUT/err.txt; exit 1; }
 cd $R
 python3 - <<PY
 import csv, glob, json
@@ -22,7 +22,7 @@ S = int((line.get("sustained") or {}).get("launches", 0))  # the sustained leg: 
 sust = [d for _, _, d in pers[len(pers) - S:]] if S else []
 timed = [d for _, _, d in pers[len(pers) - S - R:len(pers) - S]]    # the R timed regions are the R 20-turn dispatches before them (bench.py reports the median region)
 med = sorted(timed)[(R - 1) // 2]
-out = ['"# rocprofv3 --kernel-trace --stats --output-format csv -- python3 bench.py --gpus 1 --steps 20 --warmup 5 --no-cpu-baseline --no-extra-legs"',
+out = ['"# rocprofv3 --kernel-trace --stats --output-format csv -- python3 bench.py --full --gpus 1 --steps 20 --warmup 5 --no-cpu-baseline --no-extra-legs"',
        '"# persistent step-kernel dispatches of the run, in order (ns): %s"' % " ".join(str(d) for _, _, d in pers),
        '"# the LAST %d are the launches of the sustained leg (one region of %d x 150 turns): %s ns = %.2f us per turn; the line of the same run says sustained.kernel_ms = %s, sustained.ms_per_step = %s (region %s ms)"'
        % (S, S, " ".join(str(d) for d in sust), (sum(sust) / (150.0 * S) / 1e3) if S else 0.0, (line.get("sustained") or {}).get("kernel_ms"), (line.get("sustained") or {}).get("ms_per_step"), (line.get("sustained") or {}).get("region_ms")),

@@ -4,6 +4,7 @@
 # -> gpurun_out/wg256_ab.txt
 cd "$(dirname "$0")/.."
 D=$PWD/everglades-ai-wargame_amd/libevg_diag.so
+set -- --full "$@"      # the lines are read for roofline.kernel_ms (and the per-turn leg / the R regions): fields of bench.py --full
 : > gpurun_out/wg256_ab.txt
 for rep in 1 2 3 4; do
   for lanes in 64 256; do
