@@ -62,10 +62,11 @@ namespace evg {
 #define PHASE(i) STAMP(i)
 
 #include "step_common.inc"      // LDS layout of a wavefront's envs, phase fence, sorting network, small device helpers
+#include "step_rules.inc"       // the rules of a turn, written once for both lane mappings (pure register functions)
 #include "step_agents.inc"      // the scripted opponents (one device function over a view)
 #include "step_kernel.inc"      // evg_step_kernel: skeleton + the phases of a turn (step_orders / step_combat / step_move_capture / step_outputs .inc)
 
-#include "evg_step4.inc"      // the four-lanes-per-env mapping: what persistent launches of SMALL batches run (launch_step)
+#include "evg_step4.inc"        // the four-lanes-per-env mapping: what persistent launches of SMALL batches run (launch_step)
 
 #undef S
 #undef io

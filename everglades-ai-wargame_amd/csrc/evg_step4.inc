@@ -5,15 +5,17 @@
 // wavefront needs for a turn; the diagnostic library can select it at any size and in the single-turn form as well
 // (evg_diag_configure lanes = 4).  Bit-for-bit the same results as the two-lane kernel.
 //
-// THIS FILE IS A SECOND, HAND-MAINTAINED COPY OF THE WHOLE TURN (the two-lane kernel's is step_orders / step_combat / step_move_capture / step_outputs
-// .inc): a rule changed there must be changed here.  What fails when the two diverge:
+// The rules of the turn are not written here: both mappings call the same functions of step_rules.inc.  This file holds the four-lane SCHEDULE of
+// those rules -- which lane owns which groups, nodes and rows, the DPP exchanges, the LDS layout, the load and store schedules.  The tests that
+// compare it with the two-lane kernel:
 //   * tests/test_gpu_parity.py::test_four_lanes_per_env_variant_matches_oracle            every phase, both launch forms, against the oracle
 //   * ::test_small_batch_persistent_rollout_equals_the_two_lane_kernel                     what the product launches below 49 152 envs, against the two-lane kernel
 //   * ::test_damage_pool_overflow_takes_two_passes_four_lane_kernel                        the combat pool's two-pass branch of this mapping
 //   * ::test_custom_tables_vs_oracle, ::test_non_default_map_and_unit_files_through_abi    runtime tables (their persistent legs run 224 / 200 envs: this kernel)
 //   * ::test_persistent_multi_turn_rollout_equals_stepwise, ::test_config5_scripted_rollout_vs_oracle (small N), the scripted-bot tests at small N
-//   * tests/test_abi_and_host.py::test_both_lane_mappings_cite_the_same_reference_lines    (CPU) the PHASE(k) markers come in the same order in both copies and
-//     every phase cites the same anchor ranges of server.py / everglades_env.py
+//   * tests/test_abi_and_host.py::test_both_lane_mappings_cite_the_same_reference_lines    (CPU) the PHASE(k) markers come in the same order in both mappings,
+//     every phase cites the same anchor ranges of server.py / everglades_env.py, both call every rule of step_rules.inc in the same phase, and no rule
+//     formula is written outside step_rules.inc
 //
 // Mapping: lane = 4 * env_slot + 2 * player + half; one wavefront = 16 envs per workgroup; grid = N / 16.  Each (env, player)
 // side is shared by two lanes: half h owns the side's groups 6h .. 6h+5 (their words, arrival stamps, movement, aggregates,
@@ -56,27 +58,8 @@ __device__ __forceinline__ int xP(int v) { return __builtin_amdgcn_mov_dpp(v, 0x
 // 6-input sorting network (12 compare-exchanges, depth 5; checked with the 0-1 principle in tools/gen_sort12.py)
 #define EVG_SORT6_CES(CE) CE(0, 5) CE(1, 3) CE(2, 4) CE(1, 2) CE(3, 4) CE(0, 3) CE(2, 5) CE(0, 1) CE(2, 3) CE(4, 5) CE(1, 2) CE(3, 4)
 
-// what a fused scripted bot reads from the on-chip state at the start of a turn (see ChipView above)
-struct ChipView4 {
-    const Step4Lds* L;
-    int col, E, P, turn_;
-    uint64_t p1nib;
-    __device__ int node_of_slot(int slot) const { return P ? (int)((p1nib >> (4 * slot)) & 15u) : slot; }
-    __device__ int turn() const { return turn_; }
-    __device__ int loc(int k) const { const uint32_t l = L->G[k][col] & G_LOC_M; return P ? (int)((p1nib >> (4 * l)) & 15u) : (int)l; }
-    __device__ int moving(int k) const { return ((L->G[k][col] & G_MODE_M) >> G_MODE_S) == MODE_MOVING ? 1 : 0; }
-    __device__ int ctrl_slot(int slot) const { return (int)(L->NW[node_of_slot(slot)][E] & 0x3FFu) - 512; }
-    __device__ int opp_units_slot(int slot) const {
-        const uint32_t n = (uint32_t)node_of_slot(slot);
-        int u = 0;
-#pragma unroll
-        for (int k = 0; k < 12; ++k) { const uint32_t w = L->G[k][col ^ 1]; u += (w & G_LOC_M) == n ? __popc(w & G_MASK_M) : 0; }
-        return u;
-    }
-};
-
 // WPE: waves per SIMD the register allocation aims at.  4 = the whole 65 536-env batch resident (<= 128 VGPRs, 28 spilled; the
-// diagnostic experiment); 2 and 3 = 160 VGPRs, nothing spilled: the forms the product launches for up to 32 768 / 49 152 envs.
+// diagnostic experiment); 2 and 3 = 158 VGPRs, nothing spilled: the forms the product launches for up to 32 768 / 49 152 envs.
 template <typename OT, bool MULTI, int WPE = 4>
 __global__ void __launch_bounds__(WG) __attribute__((amdgpu_waves_per_eu(WPE, WPE))) evg_step4_kernel(StepArgs) {
     step_args_ptr A = (step_args_ptr)__builtin_amdgcn_kernarg_segment_ptr();
@@ -202,7 +185,7 @@ __global__ void __launch_bounds__(WG) __attribute__((amdgpu_waves_per_eu(WPE, WP
     } else if (io.gen_actions == 2) {
         // on-device scripted agents: both halves evaluate their seat's bot (identical results, identical agent objects)
         int2 rows[NA];
-        const ChipView4 view{&L, col, E, P, turn, p1nib};
+        const ChipView<Step4Lds> view{&L, col, E, P, turn, p1nib};
         const AgentTabs atabs{L.tab.nib[11], L.tab.nib[12], L.tab.nib[13], T};
         agent_rows(P ? io.policy1 : io.policy0, view, atabs, S.seed_lo, S.seed_hi, S.env_id_base + (uint32_t)e, episode, P, true, status == 0,
                    &ag_cycle, &ag_swarm, &ag_dfs, rows);
@@ -235,6 +218,7 @@ __global__ void __launch_bounds__(WG) __attribute__((amdgpu_waves_per_eu(WPE, WP
     if (play) {
         turn += 1;                                                               // server.py:214
         // ---------------- orders (server.py:218-271): each half evaluates its own rows (0..3 | 4..6) from the pre-order words
+        const uint64_t node_map = player_node_map(P, p1nib);
         if (!ABLATED(1u) && io.gen_actions == 1) {
             // drawn above: 7 DISTINCT groups in 0..11, nodes in 1..11 -> no domain checks, no "already commanded" test
             uint32_t gv[4], wv[4], nv[4], dv[4];
@@ -242,40 +226,30 @@ __global__ void __launch_bounds__(WG) __attribute__((amdgpu_waves_per_eu(WPE, WP
             for (int s = 0; s < 4; ++s) {
                 const uint32_t sh = 4u * (uint32_t)(H * 4 + s);
                 gv[s] = (gp7 >> sh) & 15u;
-                const uint32_t nid = (np7 >> sh) & 15u;
-                nv[s] = P ? (uint32_t)((p1nib >> (4 * nid)) & 15u) : nid;         // :233-234
+                nv[s] = map_node(node_map, (np7 >> sh) & 15u);
                 wv[s] = L.G[gv[s]][col];
             }
 #pragma unroll
-            for (int s = 0; s < 4; ++s) dv[s] = (uint32_t)((L.tab.adj[wv[s] & G_LOC_M] >> (4 * nv[s])) & 15u);   // :245-250
+            for (int s = 0; s < 4; ++s) dv[s] = order_dist(L.tab.adj[wv[s] & G_LOC_M], nv[s]);
 #pragma unroll
-            for (int s = 0; s < 4; ++s) {
-                const uint32_t w = wv[s];
-                if ((s < 3 || !H) && ((w & G_MODE_M) >> G_MODE_S) != MODE_MOVING && dv[s] != 0)                  // :243, :267-270
-                    L.G[gv[s]][col] = (w & ~(G_DEST_M | G_DIST_M | G_MODE_M)) | (nv[s] << G_DEST_S) | (dv[s] << G_DIST_S) | (MODE_READY << G_MODE_S);
-            }
+            for (int s = 0; s < 4; ++s)
+                if ((s < 3 || !H) && order_accepted(wv[s], dv[s])) L.G[gv[s]][col] = ordered_word(wv[s], nv[s], dv[s]);
         } else if (!ABLATED(1u)) {
-            // general rows (evg_step's tensor, scripted bots): domain of ids as in the two-lane kernel; the "already commanded"
-            // chain (:241,252) runs over half 0's rows first, its result crosses to half 1, whose rows follow
+            // general rows (evg_step's tensor, scripted bots): the "already commanded" chain (:241, :252) runs over half 0's rows first, its result
+            // crosses to half 1, whose rows follow
             int gidv[4], nidv[4], rawv[4];
             uint32_t wv[4], dv[4];
             bool condv[4], accv[4];
 #pragma unroll
             for (int s = 0; s < 4; ++s) {
-                int gid = act_mine[s].x, nid = act_mine[s].y;
-                const bool ok = (s < 3 || !H) && gid >= -12 && gid < 12 && nid >= (P ? -12 : 0) && nid < 12;
-                rawv[s] = ok ? gid + 12 : 0;
-                gid = ok ? (gid < 0 ? gid + 12 : gid) : 0;
-                nid = ok ? (nid < 0 ? nid + 12 : nid) : 0;
-                nidv[s] = P ? (int)((p1nib >> (4 * nid)) & 15u) : nid;
-                gidv[s] = gid;
-                wv[s] = L.G[gid][col];
-                condv[s] = ok;
+                gidv[s] = act_mine[s].x; nidv[s] = act_mine[s].y;
+                condv[s] = order_ids(gidv[s], nidv[s], rawv[s], node_map, P) && (s < 3 || !H);
+                wv[s] = L.G[gidv[s]][col];
             }
 #pragma unroll
             for (int s = 0; s < 4; ++s) {
-                dv[s] = (uint32_t)((L.tab.adj[wv[s] & G_LOC_M] >> (4 * nidv[s])) & 15u);
-                condv[s] = condv[s] && ((wv[s] & G_MODE_M) >> G_MODE_S) != MODE_MOVING && dv[s] != 0;
+                dv[s] = order_dist(L.tab.adj[wv[s] & G_LOC_M], (uint32_t)nidv[s]);
+                condv[s] = condv[s] && order_accepted(wv[s], dv[s]);
             }
             uint32_t used = 0;
 #pragma unroll
@@ -298,9 +272,7 @@ __global__ void __launch_bounds__(WG) __attribute__((amdgpu_waves_per_eu(WPE, WP
             for (int hh = 0; hh < 2; ++hh)
 #pragma unroll
                 for (int s = 0; s < 4; ++s)
-                    if (H == hh && accv[s])
-                        L.G[gidv[s]][col] = (wv[s] & ~(G_DEST_M | G_DIST_M | G_MODE_M)) | ((uint32_t)nidv[s] << G_DEST_S) | (dv[s] << G_DIST_S) |
-                                            (MODE_READY << G_MODE_S);
+                    if (H == hh && accv[s]) L.G[gidv[s]][col] = ordered_word(wv[s], (uint32_t)nidv[s], dv[s]);
         }
     }
     WAVE_SYNC();
@@ -496,43 +468,12 @@ __global__ void __launch_bounds__(WG) __attribute__((amdgpu_waves_per_eu(WPE, WP
                             h[8] = h[9] = h[10] = h[11] = 0.0;
                         }
                     }
-                    const uint64_t tn_s = L.tab.nib[7 + side];
-                    const uint32_t type = (uint32_t)((tn_s >> (4 * gid)) & 15u);
-                    const int ctrl_by = (int)((L.NW[node][SL >> 1] >> 10) & 3u) - 1;
-                    const int di = (int)type * 12 + (ctrl_by == side ? node : 0);                    // :592-597 (fort bonus dead)
+                    const uint32_t type = (uint32_t)((L.tab.nib[7 + side] >> (4 * gid)) & 15u);
+                    const int di = damage_index(type, L.NW[node][SL >> 1], side, node);      // node defence of the controlling side, :592-597
                     const double denom = L.tab.den[di], rcp = L.tab.rcp[di];
                     uint32_t deadmask = 0;
-                    auto apply_hits = [&](auto fast) {
-                        auto hit = [&](int sl, uint32_t d) {
-                            double loss;
-                            if constexpr (decltype(fast)::value) {
-                                const double a = (double)__umul24(10u, d);                            // exact, like 10. * tgt_dmg (d is one byte)
-                                const double q0 = a * rcp;
-                                loss = __builtin_fma(__builtin_fma(-denom, q0, a), rcp, q0);          // == a / denom (DevTables::fast_div)
-                            } else {
-                                loss = (10.0 * (double)d) / denom;                                    // :601
-                            }
-                            const double hv = h[sl] - loss;                                           // :609
-                            const bool dead = hv <= 0.0;                                              // :615-618
-                            h[sl] = dead ? 0.0 : hv;
-                            deadmask |= dead ? (1u << sl) : 0u;
-                        };
-#pragma unroll
-                        for (int sl = 0; sl < 8; ++sl) {
-                            const uint32_t sel = (uint32_t)__popc(mask & ((1u << sl) - 1u)) | 0x0C0C0C00u;
-                            hit(sl, __builtin_amdgcn_perm(d1, d0, sel));
-                        }
-                        if (gid == 11) {
-#pragma unroll
-                            for (int sl = 8; sl < 12; ++sl) {
-                                const uint32_t rank = (uint32_t)__popc(mask & ((1u << sl) - 1u));
-                                const uint32_t dA = __builtin_amdgcn_perm(d1, d0, rank | 0x0C0C0C00u);
-                                const uint32_t dB = __builtin_amdgcn_perm(0u, d2, (rank - 8u) | 0x0C0C0C00u);
-                                hit(sl, rank < 8u ? dA : dB);
-                            }
-                        }
-                    };
-                    if (fast_div) apply_hits(std::true_type{}); else apply_hits(std::false_type{});
+                    auto apply_hits = [&](auto fast) { deadmask = hit_slots<decltype(fast)::value>(h, 0, gid == 11, mask, d0, d1, d2, denom, rcp); };
+                    if (fast_div) apply_hits(std::true_type{}); else apply_hits(std::false_type{});       // quotient :601, subtraction :609; one body per form
                     const uint32_t newmask = mask & ~deadmask;
                     double2* w2 = reinterpret_cast<double2*>(row);
 #pragma unroll
@@ -541,12 +482,10 @@ __global__ void __launch_bounds__(WG) __attribute__((amdgpu_waves_per_eu(WPE, WP
                     if (gid == 11) {
 #pragma unroll
                         for (int sl = 4; sl < 6; ++sl) w2[sl] = make_double2(h[2 * sl], h[2 * sl + 1]);
-                        sum = (((sum + h[8]) + h[9]) + h[10]) + h[11];
+                        sum = health_sum_tail(sum, h);
                     }
-                    const int alive = __popc(newmask);
-                    const uint32_t avg = alive ? (uint32_t)(int)(sum / (double)alive) : 0u;          // :491 truncation
                     const uint32_t w = L.G[gid][SL];
-                    L.G[gid][SL] = (w & ~(G_MASK_M | G_AVG_M)) | (newmask << G_MASK_S) | (avg << G_AVG_S);
+                    L.G[gid][SL] = hit_word(w, newmask, sum);
                 }
             }
             WAVE_SYNC();
@@ -561,20 +500,10 @@ __global__ void __launch_bounds__(WG) __attribute__((amdgpu_waves_per_eu(WPE, WP
     if (play && !ABLATED(4u)) {
 #pragma unroll
         for (int k = 0; k < 6; ++k) {
-            const uint32_t w = gw[k];
-            const uint32_t mode = (w & G_MODE_M) >> G_MODE_S;
-            const bool alive = (w & G_MASK_M) != 0;                                    // not destroyed, :663
-            const int nd = (int)((w & G_DIST_M) >> G_DIST_S) - (int)((spd_h >> (4 * k)) & 15u);   // :671
-            const bool arrive = alive && mode == MODE_MOVING && nd <= 0;               // :678-695
-            const uint32_t w_ready = (w & ~G_MODE_M) | (MODE_MOVING << G_MODE_S);      // :664-667
-            const uint32_t w_arrive = (w & ~(G_LOC_M | G_DEST_M | G_DIST_M | G_MODE_M)) | ((w & G_DEST_M) >> G_DEST_S);
-            const uint32_t w_transit = (w & ~G_DIST_M) | ((uint32_t)(nd & 7) << G_DIST_S);
-            uint32_t nw_ = w;
-            nw_ = (alive && mode == MODE_READY) ? w_ready : nw_;
-            nw_ = (alive && mode == MODE_MOVING) ? (arrive ? w_arrive : w_transit) : nw_;
+            bool arrive;
+            gw[k] = move_group(gw[k], (spd_h >> (4 * k)) & 15u, arrive);
             if (k < 4) { const uint32_t sh = 8 * k; s_lo = arrive ? ((s_lo & ~(0xFFu << sh)) | ((uint32_t)turn << sh)) : s_lo; }
             else { const uint32_t sh = 8 * (k - 4); s_hi = arrive ? ((s_hi & ~(0xFFu << sh)) | ((uint32_t)turn << sh)) : s_hi; }
-            gw[k] = nw_;
         }
     }
     PHASE(7);
@@ -588,11 +517,8 @@ __global__ void __launch_bounds__(WG) __attribute__((amdgpu_waves_per_eu(WPE, WP
     for (int k = 0; k < 6; ++k) {
         const uint32_t w = gw[k];
         const int cnt = __popc(w & G_MASK_M);
-        const bool elig = ((w & G_MODE_M) >> G_MODE_S) != MODE_MOVING;                          // :720
-        const uint32_t ctl = (ctl_h >> (4 * k)) & 15u;
-        const uint32_t add = (elig ? (uint32_t)cnt * ctl : 0u) | ((uint32_t)cnt << 16);
-        atomicAdd(&L.u.A[w & G_LOC_M][col], add);                                               // ds_add_u32 (adds 0 for a destroyed group)
-        my_unit_score += cnt * (int)((cst_h >> (4 * k)) & 15u);                                 // :315-317
+        atomicAdd(&L.u.A[w & G_LOC_M][col], node_contribution(w, cnt, (ctl_h >> (4 * k)) & 15u));   // ds_add_u32 (0 for a destroyed group)
+        my_unit_score += unit_score(cnt, (cst_h >> (4 * k)) & 15u);
         my_alive += cnt;
     }
     my_unit_score += xH(my_unit_score);
@@ -616,28 +542,11 @@ __global__ void __launch_bounds__(WG) __attribute__((amdgpu_waves_per_eu(WPE, WP
 #pragma unroll
         for (int j = 0; j < 3; ++j) {
             const int n = 3 * q + 1 + j;
-            const bool real = n <= NN;
-            int cs = (int)(nwv[j] & 0x3FFu) - 512;
-            int cb = (int)((nwv[j] >> 10) & 3u) - 1;
-            const int cp = cpv[j], ts = tsv[j];
-            const int pts0 = (int)(a0v[j] & 0xFFFFu), pts1 = (int)(a1v[j] & 0xFFFFu);
-            const bool c0 = pts0 > 0, c1 = pts1 > 0;
-            const int pid = c0 ? 0 : 1;
-            const bool capture = real && play && (c0 != c1) && (abs(cs) < cp || pid != cb);   // :729-732
-            const int pxer = pid == 0 ? 1 : -1;
-            const int cs2 = cs + (pid == 0 ? pts0 : pts1) * pxer;                  // :748 (turn > 0 here)
-            const bool neutralize = (cs < 0) != (cs2 < 0);                         // :747-750
-            const bool full = abs(cs2) >= cp;                                      // :763-765
-            int cb2 = full ? pid : cb;
-            cb2 = (cb2 != -1 && neutralize) ? -1 : cb2;                            // :766-767
-            cs = capture ? (full ? cp * pxer : cs2) : cs;
-            cb = capture ? cb2 : cb;
-            if (capture) L.NW[n % 12][E] = (uint16_t)((uint32_t)(cs + 512) | ((uint32_t)(cb + 1) << 10));
-            const bool bcap = real && ts != -1 && cb != -1 && cb != ts;            // :299-304
-            base_cap |= bcap ? 1 : 0;
-            const int pts = real ? (abs(cs) == cp ? 2 * cp : abs(cs)) : 0;         // :305-310
-            part0 += (bcap && cb == 0 ? 1000 : 0) + (cs > 0 ? pts : 0);
-            part1 += (bcap && cb == 1 ? 1000 : 0) + (cs < 0 ? pts : 0);
+            const NodeTurn r = capture_node(nwv[j], (int)(a0v[j] & 0xFFFFu), (int)(a1v[j] & 0xFFFFu), cpv[j], tsv[j], n <= NN, play);
+            L.NW[n % 12][E] = (uint16_t)r.nw;             // (unchanged when nothing is captured; slot 0 -- n = 12 -- does not exist and is never read)
+            base_cap |= r.base_cap ? 1 : 0;
+            part0 += r.part0;
+            part1 += r.part1;
         }
     }
     // combine the quad: scores (server.py:291-317) and status (:321-328) are then known to all four lanes
@@ -648,25 +557,14 @@ __global__ void __launch_bounds__(WG) __attribute__((amdgpu_waves_per_eu(WPE, WP
     int score[2];
     score[0] = part0 + (P ? opp_unit_score : my_unit_score);
     score[1] = part1 + (P ? my_unit_score : opp_unit_score);
-    if (play) {
-        if (turn >= max_turns) status = EVG_TIME_EXPIRED;                          // :321
-        else if (my_alive + opp_alive == 0) status = EVG_ANNIHILATION;             // :324
-        else if (base_cap) status = EVG_BASE_CAPTURE;                              // :327
-    }
+    status = play ? status_after_turn(status, turn, max_turns, my_alive + opp_alive, base_cap != 0) : status;      // :321-328
     PHASE(8);
 
     // ---------------- reward / done / winner (everglades_env.py:37-61, evaluate.py:155-160)
-    float rew0, rew1;
-    int winner = EVG_WINNER_NONE;
     const bool done = status != 0;
-    if (done) {
-        winner = score[0] > score[1] ? EVG_WINNER_P0 : (score[1] > score[0] ? EVG_WINNER_P1 : EVG_WINNER_TIE);
-        rew0 = score[0] > score[1] ? 1.f : 0.f;
-        rew1 = score[1] > score[0] ? 1.f : (score[0] > score[1] ? -1.f : 0.f);
-    } else {
-        rew0 = (float)((double)score[0] / (double)EVG_MAX_SCORE);
-        rew1 = (float)((double)score[1] / (double)EVG_MAX_SCORE);
-    }
+    const TurnOutcome out = turn_outcome(done, score[0], score[1]);
+    const float rew0 = out.rew0, rew1 = out.rew1;
+    const int winner = out.winner;
     {
         float* const p_reward = io.reward;
         uint8_t* const p_done = io.done;
@@ -731,16 +629,18 @@ __global__ void __launch_bounds__(WG) __attribute__((amdgpu_waves_per_eu(WPE, WP
     // writes the turn, board slots 1..5 and groups 0..5, half 1 board slots 6..11 and groups 6..11, as int16 into the output image
     const bool want_obs = io.obs != nullptr;            // a rollout without an observation buffer skips the image and the write-out
     if (want_obs) {
-    int cs_s[6], ou_s[6];
+    const uint64_t node_map = player_node_map(P, p1nib);
+    int ns[6], ou_s[6];
+    uint32_t nw_s[6];
     const uint32_t keep_units = do_reset ? 0u : ~0u;    // an env that starts a new episode shows the game_init position
     const uint32_t opp_base = do_reset ? (L.tab.init_grp[(1 - P) * 12] & G_LOC_M) : 0xFFu;
 #pragma unroll
     for (int j = 0; j < 6; ++j) {
         const int i = 1 + j + 5 * H;                                              // slot; j = 5 of half 0 is a duplicate of slot 6 and not written
-        const int n = P ? (int)((p1nib >> (4 * i)) & 15u) : i;                    // slot i of player 1 shows node p1_node_map[i] (:437-439)
-        cs_s[j] = (int)(L.NW[n][E] & 0x3FFu) - 512;                               // control sign not mirrored
-        const uint32_t listed = L.u.A[n][col ^ 1] >> 16;                         // opposing units listed at the node, moving ones included
-        ou_s[j] = (int)((listed & keep_units) | ((uint32_t)n == opp_base ? (uint32_t)NU : 0u));
+        ns[j] = (int)map_node(node_map, (uint32_t)i);                             // slot i of player 1 shows node p1_node_map[i] (:437-439)
+        nw_s[j] = L.NW[ns[j]][E];
+        const uint32_t listed = L.u.A[ns[j]][col ^ 1] >> 16;                     // opposing units listed at the node
+        ou_s[j] = (int)((listed & keep_units) | ((uint32_t)ns[j] == opp_base ? (uint32_t)NU : 0u));
     }
     WAVE_SYNC();        // A is dead from here on: the union becomes the output image
     {
@@ -748,26 +648,21 @@ __global__ void __launch_bounds__(WG) __attribute__((amdgpu_waves_per_eu(WPE, WP
         if (!H) orow[0] = (int16_t)turn;
 #pragma unroll
         for (int j = 0; j < 6; ++j) {
-            const int i = 1 + j + 5 * H;
-            const int res = L.tab.res[P ? (int)((p1nib >> (4 * i)) & 15u) : i];
-            int16_t* o = orow + 1 + 4 * (i - 1);
+            int16_t* o = orow + 4 * (j + 5 * H) + 1;
+            int v[4];
+            obs_node(v, L.tab.res[ns[j]], nw_s[j], ou_s[j]);
             if (j < 5 || H) {
-                o[0] = (int16_t)(res & 0xFFFF);                                    // :442 (LdsTables::res holds the two flags as shown)
-                o[1] = (int16_t)(res >> 16);                                       // :443
-                o[2] = (int16_t)cs_s[j];
-                o[3] = (int16_t)ou_s[j];
+#pragma unroll
+                for (int t = 0; t < 4; ++t) o[t] = (int16_t)v[t];
             }
         }
 #pragma unroll
         for (int k = 0; k < 6; ++k) {
-            const uint32_t w = gw[k];
-            const uint32_t loc = w & G_LOC_M;
             int16_t* o = orow + 45 + 5 * (H * 6 + k);
-            o[0] = (int16_t)(P ? (uint32_t)((p1nib >> (4 * loc)) & 15u) : loc);    // :485-486
-            o[1] = (int16_t)((typ_h >> (4 * k)) & 15u);
-            o[2] = (int16_t)((w & G_AVG_M) >> G_AVG_S);
-            o[3] = (int16_t)(((w & G_MODE_M) >> G_MODE_S) == MODE_MOVING ? 1 : 0);
-            o[4] = (int16_t)__popc(w & G_MASK_M);
+            int v[5];
+            obs_group(v, gw[k], node_map, (typ_h >> (4 * k)) & 15u, __popc(gw[k] & G_MASK_M));
+#pragma unroll
+            for (int t = 0; t < 5; ++t) o[t] = (int16_t)v[t];
         }
     }
     }   // want_obs

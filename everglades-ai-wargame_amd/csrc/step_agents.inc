@@ -146,17 +146,18 @@ struct ObsView {
     __device__ int opp_units_slot(int slot) const { return (int)o[4 * slot]; }
 };
 
-// the same quantities taken from the on-chip state at the start of a turn (fused rollout)
-template <int LPW>
+// the same quantities taken from the on-chip state at the start of a turn (fused rollout), over either lane mapping's LDS (StepLds<LPW> / Step4Lds:
+// G = group words [gid][side column], NW = node words [node][env column])
+template <typename Lds>
 struct ChipView {
-    const StepLds<LPW>* L;
+    const Lds* L;
     int col, E, P, turn_;
     uint64_t p1nib;
     __device__ int node_of_slot(int slot) const { return P ? (int)((p1nib >> (4 * slot)) & 15u) : slot; }
     __device__ int turn() const { return turn_; }
     __device__ int loc(int k) const { const uint32_t l = L->G[k][col] & G_LOC_M; return P ? (int)((p1nib >> (4 * l)) & 15u) : (int)l; }
     __device__ int moving(int k) const { return ((L->G[k][col] & G_MODE_M) >> G_MODE_S) == MODE_MOVING ? 1 : 0; }
-    __device__ int ctrl_slot(int slot) const { return (int)(L->NW[node_of_slot(slot)][E] & 0x3FFu) - 512; }
+    __device__ int ctrl_slot(int slot) const { return node_cs(L->NW[node_of_slot(slot)][E]); }
     __device__ int opp_units_slot(int slot) const {                        // units of every non-destroyed opposing group listed at the node
         const uint32_t n = (uint32_t)node_of_slot(slot);
         int u = 0;

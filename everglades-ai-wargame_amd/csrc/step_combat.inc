@@ -293,46 +293,12 @@
                             h[8] = h[9] = h[10] = h[11] = 0.0;
                         }
                     }
-                    const uint64_t tn_s = L.tab.nib[7 + side];
-                    const uint32_t type = (uint32_t)((tn_s >> (4 * gid)) & 15u);
-                    const int ctrl_by = (int)((L.NW[node][SL >> 1] >> 10) & 3u) - 1;
-                    const int di = (int)type * 12 + (ctrl_by == side ? node : 0);                    // :592-597 (fort bonus dead)
+                    const uint32_t type = (uint32_t)((L.tab.nib[7 + side] >> (4 * gid)) & 15u);
+                    const int di = damage_index(type, L.NW[node][SL >> 1], side, node);      // node defence of the controlling side, :592-597
                     const double denom = L.tab.den[di], rcp = L.tab.rcp[di];
-                    // Slot sl holds the unit of rank popc(mask below sl); its damage byte is picked with one v_perm_b32 (selector =
-                    // rank, the other three selector bytes 0x0C = constant zero).  A slot whose unit is already dead picks the byte
-                    // of the next alive unit: harmless, its health is 0.0 and stays 0.0 (0 - loss clamps to 0), its mask bit stays clear.
                     uint32_t deadmask = 0;
-                    auto apply_hits = [&](auto fast) {           // one straight-line body per quotient form (wave-uniform choice)
-                        auto hit = [&](int sl, uint32_t d) {
-                            double loss;
-                            if constexpr (decltype(fast)::value) {
-                                const double a = (double)__umul24(10u, d);                            // exact, like 10. * tgt_dmg (d is one byte)
-                                const double q0 = a * rcp;
-                                loss = __builtin_fma(__builtin_fma(-denom, q0, a), rcp, q0);          // == a / denom (DevTables::fast_div)
-                            } else {
-                                loss = (10.0 * (double)d) / denom;                                    // :601
-                            }
-                            const double hv = h[sl] - loss;                                           // :609
-                            const bool dead = hv <= 0.0;                                              // :615-618
-                            h[sl] = dead ? 0.0 : hv;
-                            deadmask |= dead ? (1u << sl) : 0u;
-                        };
-#pragma unroll
-                        for (int sl = 0; sl < 8; ++sl) {         // rank <= sl < 8: bytes of a0, a1
-                            const uint32_t sel = (uint32_t)__popc(mask & ((1u << sl) - 1u)) | 0x0C0C0C00u;
-                            hit(sl, __builtin_amdgcn_perm(a1, a0, sel));
-                        }
-                        if (gid == 11) {                         // the 12-unit group: slots 8..11, ranks up to 11
-#pragma unroll
-                            for (int sl = 8; sl < 12; ++sl) {
-                                const uint32_t rank = (uint32_t)__popc(mask & ((1u << sl) - 1u));
-                                const uint32_t dA = __builtin_amdgcn_perm(a1, a0, rank | 0x0C0C0C00u);
-                                const uint32_t dB = __builtin_amdgcn_perm(0u, a2, (rank - 8u) | 0x0C0C0C00u);
-                                hit(sl, rank < 8u ? dA : dB);
-                            }
-                        }
-                    };
-                    if (fast_div) apply_hits(std::true_type{}); else apply_hits(std::false_type{});
+                    auto apply_hits = [&](auto fast) { deadmask = hit_slots<decltype(fast)::value>(h, 0, gid == 11, mask, a0, a1, a2, denom, rcp); };
+                    if (fast_div) apply_hits(std::true_type{}); else apply_hits(std::false_type{});       // quotient :601, subtraction :609; one body per form
                     const uint32_t newmask = mask & ~deadmask;
                     double2* w2 = reinterpret_cast<double2*>(row);
 #pragma unroll
@@ -341,12 +307,10 @@
                     if (gid == 11) {
 #pragma unroll
                         for (int sl = 4; sl < 6; ++sl) w2[sl] = make_double2(h[2 * sl], h[2 * sl + 1]);
-                        sum = (((sum + h[8]) + h[9]) + h[10]) + h[11];
+                        sum = health_sum_tail(sum, h);
                     }
-                    const int alive = __popc(newmask);
-                    const uint32_t avg = alive ? (uint32_t)(int)(sum / (double)alive) : 0u;          // :491 truncation
                     const uint32_t w = L.G[gid][SL];
-                    L.G[gid][SL] = (w & ~(G_MASK_M | G_AVG_M)) | (newmask << G_MASK_S) | (avg << G_AVG_S);
+                    L.G[gid][SL] = hit_word(w, newmask, sum);
                 }
             }
             if (split_last) {
@@ -380,33 +344,12 @@
                             const double2 v0 = r2[0], v1 = r2[1];
                             h[0] = v0.x; h[1] = v0.y; h[2] = v1.x; h[3] = v1.y;
                         }
-                        const uint64_t tn_s = L.tab.nib[7 + side];
-                        const uint32_t type = (uint32_t)((tn_s >> (4 * gid)) & 15u);
-                        const int ctrl_by = (int)((L.NW[node][SL >> 1] >> 10) & 3u) - 1;
-                        const int di = (int)type * 12 + (ctrl_by == side ? node : 0);                // :592-597 (fort bonus dead)
+                        const uint32_t type = (uint32_t)((L.tab.nib[7 + side] >> (4 * gid)) & 15u);
+                        const int di = damage_index(type, L.NW[node][SL >> 1], side, node);      // node defence of the controlling side, :592-597
                         const double denom = L.tab.den[di], rcp = L.tab.rcp[di];
-                        uint32_t deadmask = 0;
-                        auto apply_hits4 = [&](auto fast) {
-#pragma unroll
-                            for (int j = 0; j < 4; ++j) {
-                                const uint32_t sl = (uint32_t)(4 * hf + j);                          // this lane's slot
-                                const uint32_t sel = (uint32_t)__popc(mask & ((1u << sl) - 1u)) | 0x0C0C0C00u;
-                                const uint32_t d = __builtin_amdgcn_perm(a1, a0, sel);
-                                double loss;
-                                if constexpr (decltype(fast)::value) {
-                                    const double a = (double)__umul24(10u, d);
-                                    const double q0 = a * rcp;
-                                    loss = __builtin_fma(__builtin_fma(-denom, q0, a), rcp, q0);
-                                } else {
-                                    loss = (10.0 * (double)d) / denom;                                // :601
-                                }
-                                const double hv = h[j] - loss;                                        // :609
-                                const bool dead = hv <= 0.0;                                          // :615-618
-                                h[j] = dead ? 0.0 : hv;
-                                deadmask |= dead ? (1u << sl) : 0u;
-                            }
-                        };
-                        if (fast_div) apply_hits4(std::true_type{}); else apply_hits4(std::false_type{});
+                        uint32_t deadmask = 0;                                                       // of this lane's slots
+                        auto apply_hits4 = [&](auto fast) { deadmask = hit_slots<decltype(fast)::value>(h, 4 * hf, false, mask, a0, a1, 0u, denom, rcp); };
+                        if (fast_div) apply_hits4(std::true_type{}); else apply_hits4(std::false_type{});     // quotient :601, subtraction :609
                         double2* w2 = reinterpret_cast<double2*>(row);
                         w2[0] = make_double2(h[0], h[1]);
                         w2[1] = make_double2(h[2], h[3]);
@@ -414,12 +357,7 @@
                         const double mine = (h[0] + h[1]) + (h[2] + h[3]);
                         const double other = __hiloint2double(xchg1(__double2hiint(mine)), xchg1(__double2loint(mine)));
                         const double sum = hf ? other + mine : mine + other;                          // left half + right half (np.sum's pairwise order)
-                        const int alive = __popc(newmask);
-                        const uint32_t avg = alive ? (uint32_t)(int)(sum / (double)alive) : 0u;      // :491 truncation
-                        if (hf == 0) {
-                            const uint32_t w = L.G[gid][SL];
-                            L.G[gid][SL] = (w & ~(G_MASK_M | G_AVG_M)) | (newmask << G_MASK_S) | (avg << G_AVG_S);
-                        }
+                        if (hf == 0) L.G[gid][SL] = hit_word(L.G[gid][SL], newmask, sum);
                     }
                 }
             }

@@ -58,29 +58,11 @@ __device__ __forceinline__ double np_sum8(const double* h) {
 // counter passes,
 // profiles/r05_a_health_row_bytes.txt): the health-row reads that reach the fabric drop by a third (FETCH_SIZE 187 -> 130 B per env-step; the fabric moves
 // whole 128-byte lines, so twice that in bytes), 1 528 -> 1 421 B per env-step in all, at the same time per turn (14.62 against 14.63 us).  The recorded orders
-// (7 x 8 bytes per lane) stay ordinary stores: non-temporal 8-byte stores made the launch ERRATIC (14.9 us in some runs, 19-20 us in others: EVG_NT_OUTPUTS=2,
-// `make nt`), and they are 112 bytes against 840.  EVG_NT_OUTPUTS=0 builds the all-temporal form for the A/B.
-#ifndef EVG_STAGE_ORDERS
-#define EVG_STAGE_ORDERS 0
-#endif
-#ifndef EVG_NT_OUTPUTS
-#define EVG_NT_OUTPUTS 1
-#endif
+// (7 x 8 bytes per lane) stay ordinary stores: non-temporal 8-byte stores made the launch ERRATIC (14.9 us in some runs, 19-20 us in others; round 5), and
+// they are 112 bytes against 840.
 typedef uint32_t evg_v4u __attribute__((ext_vector_type(4)));
-typedef uint32_t evg_v2u __attribute__((ext_vector_type(2)));
 __device__ __forceinline__ void stream_store16(void* dst, uint32_t x, uint32_t y, uint32_t z, uint32_t w) {
-#if EVG_NT_OUTPUTS >= 1
     __builtin_nontemporal_store((evg_v4u){x, y, z, w}, reinterpret_cast<evg_v4u*>(dst));
-#else
-    *reinterpret_cast<uint4*>(dst) = make_uint4(x, y, z, w);
-#endif
-}
-__device__ __forceinline__ void stream_store8(void* dst, uint32_t x, uint32_t y) {
-#if EVG_NT_OUTPUTS >= 2
-    __builtin_nontemporal_store((evg_v2u){x, y}, reinterpret_cast<evg_v2u*>(dst));
-#else
-    *reinterpret_cast<uint2*>(dst) = make_uint2(x, y);
-#endif
 }
 
 template <typename OT>

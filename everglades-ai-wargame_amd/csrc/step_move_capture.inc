@@ -8,22 +8,12 @@
 #pragma unroll
     for (int k = 0; k < 12; ++k) gw[k] = envlane ? L.G[k][col] : 0u;
     if (play && !ABLATED(4u)) {
-        static_assert(MODE_READY == 1 && MODE_MOVING == 2, "ready -> moving is +1 in the mode field; bit 1 of the field is `moving`");
 #pragma unroll
         for (int k = 0; k < 12; ++k) {
-            const uint32_t w = gw[k];
-            const bool alive = (w & G_MASK_M) != 0;                                    // not destroyed, :663
-            const uint32_t spd = (uint32_t)((spd_n >> (4 * k)) & 15u) << G_DIST_S;     // the group's speed, aligned with the distance field
-            const bool ready = alive && (w & G_MODE_M) == (MODE_READY << G_MODE_S);
-            const bool moving = alive && (w & (MODE_MOVING << G_MODE_S)) != 0;
-            const bool arrive = moving && (w & G_DIST_M) <= spd;                       // :671, :678-695
-            const uint32_t w_arrive = (w & ~(G_LOC_M | G_DEST_M | G_DIST_M | G_MODE_M)) | ((w & G_DEST_M) >> G_DEST_S);
-            uint32_t nw_ = ready ? w + (1u << G_MODE_S) : w;                           // :664-667: moves from the next turn on
-            nw_ = moving ? w - spd : nw_;                                              // in transit: distance_remaining -= speed (> 0 left)
-            nw_ = arrive ? w_arrive : nw_;
+            bool arrive;
+            gw[k] = move_group(gw[k], (uint32_t)((spd_n >> (4 * k)) & 15u), arrive);
             const uint32_t sh = 8 * (k & 3);
             st[k >> 2] = arrive ? ((st[k >> 2] & ~(0xFFu << sh)) | ((uint32_t)turn << sh)) : st[k >> 2];
-            gw[k] = nw_;
         }
     }
     PHASE(7);
@@ -38,11 +28,8 @@
         int cnt = __popc(w & G_MASK_M);
         asm volatile("" : "+v"(cnt));           // keep the count in its register for the observation (the compiler would recompute it there)
         cntv[k] = cnt;
-        const bool elig = ((w & G_MODE_M) >> G_MODE_S) != MODE_MOVING;                          // :720
-        const uint32_t ctl = (uint32_t)((ctl_n >> (4 * k)) & 15u);
-        const uint32_t add = (elig ? (uint32_t)cnt * ctl : 0u) | ((uint32_t)cnt << 16);
-        if (envlane) atomicAdd(&L.u.A[w & G_LOC_M][lane], add);                                 // ds_add_u32 (adds 0 for a destroyed group)
-        my_unit_score += cnt * (int)((cst_n >> (4 * k)) & 15u);                                 // :315-317
+        if (envlane) atomicAdd(&L.u.A[w & G_LOC_M][lane], node_contribution(w, cnt, (uint32_t)((ctl_n >> (4 * k)) & 15u)));   // ds_add_u32 (0 for a destroyed group)
+        my_unit_score += unit_score(cnt, (uint32_t)((cst_n >> (4 * k)) & 15u));
         my_alive += cnt;
     }
     WAVE_SYNC();
@@ -70,30 +57,13 @@
         }
 #pragma unroll
         for (int j = 0; j < 6; ++j) {
-            const bool real = j > 0 || P != 0;
-            int cs = (int)(nwv[j] & 0x3FFu) - 512;
-            uint32_t cb1 = (nwv[j] >> 10) & 3u;                                    // controlledBy + 1
-            const int cp = cpv[j], ts = tsv[j];
-            const int pts0 = (int)(a0v[j] & 0xFFFFu), pts1 = (int)(a1v[j] & 0xFFFFu);
-            const bool c0 = pts0 > 0, c1 = pts1 > 0;                               // ctr >= 1 (control >= 1)
-            const uint32_t pid1 = c0 ? 1u : 2u;                                    // capturing player + 1
-            const bool capture = real && play && (c0 != c1) && (abs(cs) < cp || pid1 != cb1);   // :729-732
-            const int cs2 = cs + (pts0 - pts1);                                    // :748 (turn > 0 here): exactly one of the two is non-zero
-            const bool neutralize = (cs ^ cs2) < 0;                                // :747-750: the sign bit changed
-            const bool full = abs(cs2) >= cp;                                      // :763-765
-            const uint32_t cb1n = neutralize ? 0u : (full ? pid1 : cb1);           // :766-767
-            const int csn = full ? (c0 ? cp : -cp) : cs2;
-            cs = capture ? csn : cs;
-            cb1 = capture ? cb1n : cb1;
+            const NodeTurn r = capture_node(nwv[j], (int)(a0v[j] & 0xFFFFu), (int)(a1v[j] & 0xFFFFu), cpv[j], tsv[j], j > 0 || P != 0, play);
             // (an unconditional store: the word is unchanged when nothing is captured; row 0 does not exist and is never read.  Helper lanes of the
             // 16-envs-per-wave variant alias env slot 0 and must not store)
-            if (envlane) L.NW[nb + j][E] = (uint32_t)(cs + 512) | (cb1 << 10);
-            const bool bcap = real && ts != -1 && cb1 != 0u && (int)cb1 != ts + 1;  // :299-304
-            base_cap |= bcap ? 1 : 0;
-            const int acs = abs(cs);
-            const int pts = real ? acs + (acs == cp ? cp : 0) : 0;                 // :305-310
-            part0 += (bcap && cb1 == 1u ? 1000 : 0) + (cs > 0 ? pts : 0);
-            part1 += (bcap && cb1 == 2u ? 1000 : 0) + (cs < 0 ? pts : 0);
+            if (envlane) L.NW[nb + j][E] = r.nw;
+            base_cap |= r.base_cap ? 1 : 0;
+            part0 += r.part0;
+            part1 += r.part1;
         }
     }
     // combine the pair: scores (server.py:291-317) and status (:321-328) are then known to both lanes
@@ -104,31 +74,17 @@
     int score[2];
     score[0] = part0 + (P ? opp_unit_score : my_unit_score);
     score[1] = part1 + (P ? my_unit_score : opp_unit_score);
-    {   // status precedence TimeExpired > Annihilation > BaseCapture (:321-328), as selects: three nested divergent branches otherwise
-        const int st_new = turn >= max_turns ? EVG_TIME_EXPIRED : (my_alive + opp_alive == 0 ? EVG_ANNIHILATION : (base_cap ? EVG_BASE_CAPTURE : status));
-        status = play ? st_new : status;
-    }
+    status = play ? status_after_turn(status, turn, max_turns, my_alive + opp_alive, base_cap != 0) : status;      // :321-328
     if constexpr (MT) {
         if (play && mt_lane && turn % 10 == 0) (void)mt_randint(mt, 2u * NG + 1u);  // :337-338 focus draw: unobservable, but it consumes output
     }
     PHASE(8);
 
     // ---------------- reward / done / winner (everglades_env.py:37-61, evaluate.py:155-160)
-    float rew0, rew1;
-    int winner = EVG_WINNER_NONE;
     const bool done = status != 0;
-    if (done) {
-        winner = score[0] > score[1] ? EVG_WINNER_P0 : (score[1] > score[0] ? EVG_WINNER_P1 : EVG_WINNER_TIE);
-        rew0 = score[0] > score[1] ? 1.f : 0.f;
-        rew1 = score[1] > score[0] ? 1.f : (score[0] > score[1] ? -1.f : 0.f);
-    } else {
-        // scores[p] / 3700 (everglades_env.py:63-64) rounded to the float32 the reward tensor holds: the product with the rounded
-        // reciprocal differs from the float64 quotient by an ulp of float64 at most, which never crosses a float32 rounding
-        // boundary for an integer score below 2^22 (checked exhaustively: tests/test_abi_and_host.py)
-        constexpr double kInvMaxScore = 1.0 / (double)EVG_MAX_SCORE;
-        rew0 = (float)((double)score[0] * kInvMaxScore);
-        rew1 = (float)((double)score[1] * kInvMaxScore);
-    }
+    const TurnOutcome out = turn_outcome(done, score[0], score[1]);
+    const float rew0 = out.rew0, rew1 = out.rew1;
+    const int winner = out.winner;
     {
         // the output pointers are fetched together (one scalar-load batch), not one by one inside the branches below
         float* const p_reward = io.reward;

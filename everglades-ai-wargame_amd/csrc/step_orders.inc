@@ -16,7 +16,7 @@
                 for (int i = 0; i < NA; ++i) act[i] = act_in[i];         // drawn in the prologue, under the state loads
             }
         } else {                                        // on-device scripted agents of both seats (evg_rollout_policies, fused)
-            const ChipView<LPW> view{&L, col, E, P, turn, p1nib};
+            const ChipView<StepLds<LPW>> view{&L, col, E, P, turn, p1nib};
             // both seats' policy ids as scalars, selected per lane (the compiler would otherwise turn the select into a per-lane
             // global load from the argument segment, and wait for vmcnt(0) -- i.e. for last turn's stores -- in front of its use)
             int pol0 = io.policy0, pol1 = io.policy1;
@@ -34,38 +34,10 @@
                 S.agent_cycle[ai_] = ag_cycle; S.agent_swarm[ai_] = ag_swarm; S.agent_dfs[ai_] = ag_dfs;
             }
         }
-#if EVG_STAGE_ORDERS
-        // Round-6 experiment (`make stage`, profiles/r06_d_observation_phase.txt): the wave's 64 x 7 recorded rows are ONE contiguous 3 584-byte piece of the
-        // output ([env][player][7][2] of 32 consecutive envs), but a lane's own 56 bytes lie 56 bytes from its neighbour's: seven 8-byte stores per lane touch
-        // 28 lines each, 196 line requests per wave and turn -- as many as the whole observation write-out.  Staged through the union (free between the previous
-        // turn's write-out and combat) they leave as 16 bytes per lane: 28 line requests.
-        if (io.gen_actions == 1 && LPW == WG && !SEAT && io.actions_out) {
-            uint2* stage = reinterpret_cast<uint2*>(&L.u);
-#pragma unroll
-            for (int i = 0; i < NA; ++i) stage[lane * NA + i] = make_uint2((uint32_t)act[i].x, (uint32_t)act[i].y);
-            WAVE_SYNC();
-            const uint4* src = reinterpret_cast<const uint4*>(&L.u);
-            uint4* dst = reinterpret_cast<uint4*>(reinterpret_cast<int2*>(io.actions_out) + (size_t)e0 * 2 * NA);
-            const int nvec = nvalid * NA;                      // 16-byte pieces: two rows each, 14 rows per env
-#pragma unroll
-            for (int j = 0; j < (WG * NA / 2 + WG - 1) / WG; ++j) {
-                const int v = lane + j * WG;
-                if (v < nvec) {
-                    const uint4 q = src[v];
-#if EVG_STAGE_ORDERS >= 2
-                    stream_store16(dst + v, q.x, q.y, q.z, q.w);          // non-temporal, like the observation rows
-#else
-                    dst[v] = q;                                          // ordinary store, like the per-lane rows it replaces
-#endif
-                }
-            }
-            WAVE_SYNC();
-        } else
-#endif
         if (valid && io.actions_out) {
             int2* ao = reinterpret_cast<int2*>(io.actions_out) + ((size_t)e * 2 + P) * NA;
 #pragma unroll
-            for (int i = 0; i < NA; ++i) stream_store8(ao + i, (uint32_t)act[i].x, (uint32_t)act[i].y);
+            for (int i = 0; i < NA; ++i) ao[i] = act[i];
         }
     } else {
 #pragma unroll
@@ -83,29 +55,26 @@
         // of every row can be taken from the pre-order words; rows interact only through test 1 (an id already
         // commanded this turn) and, for aliased ids, through the order of the writes (the later row wins, as in
         // the reference).  That makes the 7 LDS lookups independent instead of a 7-deep dependent chain.
+        const uint64_t node_map = player_node_map(P, p1nib);
         if (!ABLATED(1u) && io.gen_actions == 1) {
             // Orders drawn in this kernel by gen_random_rows: 7 DISTINCT group ids in 0..11 and node ids in 1..11 by construction, so
             // the domain checks, the Python-list negative indices and the "already commanded this turn" test of the general path
             // below cannot trigger; every row is independent.
             uint32_t wv[NA], nv[NA], dv[NA];
-            // (the node map of this lane's player as ONE table -- identity for player 0 --, so that the seven lookups are straight-line code: written as
-            // `P ? map[y] : y` each of them became a divergent branch with its own exec-mask region)
-            const uint64_t map_n = P ? p1nib : 0xBA9876543210ull;
 #pragma unroll
             for (int i = 0; i < NA; ++i) {
-                nv[i] = (uint32_t)((map_n >> (4 * act[i].y)) & 15u);                                 // :233-234
+                nv[i] = map_node(node_map, (uint32_t)act[i].y);
                 wv[i] = L.G[act[i].x][lane];
             }
 #pragma unroll
-            for (int i = 0; i < NA; ++i) dv[i] = (uint32_t)((L.tab.adj[wv[i] & G_LOC_M] >> (4 * nv[i])) & 15u);   // :245-250
+            for (int i = 0; i < NA; ++i) dv[i] = order_dist(L.tab.adj[wv[i] & G_LOC_M], nv[i]);
 #pragma unroll
             for (int i = 0; i < NA; ++i) {
-                const uint32_t w = wv[i];
                 // (seven DISTINCT groups: every word is written once, so a rejected row can store the word it read -- an unconditional LDS store of a select
                 // instead of a predicated one: no exec-mask juggling and no branch per row)
-                const bool accept = ((w & G_MODE_M) >> G_MODE_S) != MODE_MOVING && dv[i] != 0;       // :243, :267-270
-                const uint32_t ordered = (w & ~(G_DEST_M | G_DIST_M | G_MODE_M)) | (nv[i] << G_DEST_S) | (dv[i] << G_DIST_S) | (MODE_READY << G_MODE_S);
-                L.G[act[i].x][lane] = accept ? ordered : w;
+                const bool accept = order_accepted(wv[i], dv[i]);
+                const uint32_t ordered = ordered_word(wv[i], nv[i], dv[i]);
+                L.G[act[i].x][lane] = accept ? ordered : wv[i];
             }
         } else if (!ABLATED(1u)) {
             int gidv[NA], nidv[NA], rawv[NA];
@@ -113,30 +82,18 @@
             bool okv[NA];
 #pragma unroll
             for (int i = 0; i < NA; ++i) {
-                int gid = act[i].x, nid = act[i].y;
-                // Domain: ids in [-12, 11] behave like the reference's Python lists (a negative index counts from the end:
-                // groups[gid] at :235, p1_node_map[nid] at :92 for player 1); for player 0 a negative node id matches no
-                // connection; anything else would raise in the reference and is an invalid order here.
-                okv[i] = gid >= -12 && gid < 12 && nid >= (P ? -12 : 0) && nid < 12;
-                rawv[i] = okv[i] ? gid + 12 : 0;                                 // used_swarms keeps the ids as given (:241,252)
-                gid = okv[i] ? (gid < 0 ? gid + 12 : gid) : 0;
-                nid = okv[i] ? (nid < 0 ? nid + 12 : nid) : 0;
-                nidv[i] = P ? (int)((p1nib >> (4 * nid)) & 15u) : nid;           // :233-234
-                gidv[i] = gid;
-                wv[i] = L.G[gid][lane];
+                gidv[i] = act[i].x; nidv[i] = act[i].y;
+                okv[i] = order_ids(gidv[i], nidv[i], rawv[i], node_map, P);
+                wv[i] = L.G[gidv[i]][lane];
             }
 #pragma unroll
-            for (int i = 0; i < NA; ++i)
-                dv[i] = (uint32_t)((L.tab.adj[wv[i] & G_LOC_M] >> (4 * nidv[i])) & 15u);   // test3 + distance, :245-250
-            uint32_t used = 0;
+            for (int i = 0; i < NA; ++i) dv[i] = order_dist(L.tab.adj[wv[i] & G_LOC_M], (uint32_t)nidv[i]);
+            uint32_t used = 0;                                                   // the "already commanded this turn" chain (:241, :252)
 #pragma unroll
             for (int i = 0; i < NA; ++i) {
-                const uint32_t w = wv[i];
-                const bool accept = okv[i] && !((used >> rawv[i]) & 1u) && ((w & G_MODE_M) >> G_MODE_S) != MODE_MOVING && dv[i] != 0;
+                const bool accept = okv[i] & !((used >> rawv[i]) & 1u) & order_accepted(wv[i], dv[i]);
                 used |= (accept ? 1u : 0u) << rawv[i];
-                if (accept)                                                      // :267-270
-                    L.G[gidv[i]][lane] = (w & ~(G_DEST_M | G_DIST_M | G_MODE_M)) | ((uint32_t)nidv[i] << G_DEST_S) | (dv[i] << G_DIST_S) |
-                                         (MODE_READY << G_MODE_S);
+                if (accept) L.G[gidv[i]][lane] = ordered_word(wv[i], (uint32_t)nidv[i], dv[i]);
             }
         }
     }

@@ -14,11 +14,11 @@
 #pragma unroll
     for (int n = 1; n <= NN; ++n) {
         nw_n[n] = L.NW[n][E];
-        ou_n[n] = L.u.A[n][col ^ 1];                    // high half: opposing units listed at the node, moving ones included (:446-449)
+        ou_n[n] = L.u.A[n][col ^ 1];                    // high half: opposing units listed at the node
         res_n[n] = (uint32_t)L.tab.res[n];              // DEFENSE flag | OBSERVE flag << 16
     }
     const uint64_t slot_n = P ? L.tab.nib[10] : 0xBA9876543210ull;     // nibble n = board slot of node n in this player's view
-    const uint64_t own_n = P ? p1nib : 0xBA9876543210ull;              // nibble n = node n in this player's numbering (:485-486)
+    const uint64_t own_n = player_node_map(P, p1nib);                  // nibble n = node n in this player's numbering (:485-486)
     WAVE_SYNC();        // A is dead from here on: the union becomes the output image
     // one-seat form: the image is [env][105], built by the caller's lane only.  (Splitting that row between the two lanes of the pair -- half the
     // instructions -- and the 28 MB less to write change nothing measurable: 26.7 us either way, like evg_step with both rows; a single-turn launch
@@ -29,21 +29,18 @@
 #pragma unroll
         for (int n = 1; n <= NN; ++n) {
             int16_t* o = orow + 4 * (int)((slot_n >> (4 * n)) & 15u) - 3;
-            o[0] = (int16_t)(res_n[n] & 0xFFFFu);                                  // :442
-            o[1] = (int16_t)(res_n[n] >> 16);                                      // :443
-            o[2] = (int16_t)((int)(nw_n[n] & 0x3FFu) - 512);                       // control sign not mirrored
-            o[3] = (int16_t)(ou_n[n] >> 16);
+            int v[4];
+            obs_node(v, (int)res_n[n], nw_n[n], (int)(ou_n[n] >> 16));
+#pragma unroll
+            for (int j = 0; j < 4; ++j) o[j] = (int16_t)v[j];
         }
-        static_assert(MODE_MOVING == 2 && MODE_READY == 1 && MODE_IDLE == 0, "bit 1 of the mode field is the `moving` flag");
 #pragma unroll
         for (int k = 0; k < 12; ++k) {
-            const uint32_t w = gw[k];
             int16_t* o = orow + 45 + 5 * k;
-            o[0] = (int16_t)((own_n >> (4 * (w & G_LOC_M))) & 15u);
-            o[1] = (int16_t)((typ_n >> (4 * k)) & 15u);
-            o[2] = (int16_t)((w & G_AVG_M) >> G_AVG_S);
-            o[3] = (int16_t)((w >> (G_MODE_S + 1)) & 1u);
-            o[4] = (int16_t)cntv[k];
+            int v[5];
+            obs_group(v, gw[k], own_n, (uint32_t)((typ_n >> (4 * k)) & 15u), cntv[k]);
+#pragma unroll
+            for (int j = 0; j < 5; ++j) o[j] = (int16_t)v[j];
         }
     }
     }   // want_obs

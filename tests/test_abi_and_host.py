@@ -596,14 +596,52 @@ def test_bench_line_says_where_every_rank_sat_and_what_the_reference_does():
 
 
 def test_both_lane_mappings_cite_the_same_reference_lines():
-    """csrc/evg_step4.inc (four lanes per env) is a hand-maintained second copy of the turn next to the two-lane fragments (step_orders / step_combat /
-    step_move_capture / step_outputs .inc).  The parity suite keeps their RESULTS equal on the GPU; this table-driven check keeps their STRUCTURE comparable on
-    the CPU: both walk through the phase markers PHASE(1) .. PHASE(13) in the same order, and between the same two markers both cite the same anchor ranges of
-    the reference (server.py / everglades_env.py line ranges in the comments) -- so a rule that moves or is re-derived in one copy shows up as a mismatch here."""
+    """The turn has two lane mappings -- the two-lane fragments (step_orders / step_combat / step_move_capture / step_outputs .inc) and the four-lane
+    csrc/evg_step4.inc -- and ONE set of rules, csrc/step_rules.inc, that both call.  The parity suite keeps their RESULTS equal on the GPU; this check keeps
+    their STRUCTURE equal on the CPU: both walk through the phase markers PHASE(1) .. PHASE(13) in the same order; between the same two markers both cite the
+    same anchor ranges of the reference (server.py / everglades_env.py line ranges in the comments, the comments of the rules a phase calls included); both
+    call every rule of the header, in the same phases; and no rule formula is written outside the header -- so a rule re-derived in one mapping fails here."""
     csrc = os.path.join(ROOT, "everglades-ai-wargame_amd", "csrc")
     two = "".join(open(os.path.join(csrc, f)).read() for f in ("step_orders.inc", "step_combat.inc", "step_move_capture.inc", "step_outputs.inc"))
     four = open(os.path.join(csrc, "evg_step4.inc")).read()
     four = four[four.index("if (MULTI) { PHASE(0); }"):]                  # the turn loop (the prologue's STAMP(0) / PHASE(0) belong to step_kernel.inc there)
+    rules_src = open(os.path.join(csrc, "step_rules.inc")).read()
+
+    def strip_comments(text):
+        return re.sub(r"//[^\n]*", "", text)
+
+    # the rules header: function name -> its text (the comment block above it, its signature and its body)
+    rules = {}
+    lines = rules_src.split("\n")
+    for i, line in enumerate(lines):
+        m = re.match(r"__device__ __forceinline__ [\w:<>]+ (\w+)\(", line)
+        if not m:
+            continue
+        j = i
+        while j > 0 and (lines[j - 1].startswith("//") or lines[j - 1].startswith("template")):
+            j -= 1
+        k, depth = i, 0
+        while True:
+            code = strip_comments(lines[k])
+            depth += code.count("{") - code.count("}")
+            if depth == 0 and "}" in code:
+                break
+            k += 1
+        rules[m.group(1)] = "\n".join(lines[j:k + 1])
+    assert len(rules) >= 20, sorted(rules)
+
+    def calls(text):
+        code = strip_comments(text)
+        return {f for f in rules if re.search(r"\b%s\s*[<(]" % f, code)}
+
+    def closure(text):                                  # the rules a piece of code calls, directly or through other rules
+        out, todo = set(), calls(text)
+        while todo:
+            f = todo.pop()
+            if f not in out:
+                out.add(f)
+                todo |= calls(rules[f].split("{", 1)[1]) - out
+        return out
 
     def phases(src):
         parts = re.split(r"PHASE\((\d+)\);", src)
@@ -637,11 +675,41 @@ def test_both_lane_mappings_cite_the_same_reference_lines():
     o2, t2 = phases(two)
     o4, t4 = phases(four)
     assert o2 == list(range(1, 14)) and o4[-13:] == list(range(1, 14)), (o2, o4)
+    # a phase's text includes the rules it calls: a citation that lives in the header counts for every caller
+    t2 = {k: v + "\n".join(rules[f] for f in sorted(closure(v))) for k, v in t2.items()}
+    t4 = {k: v + "\n".join(rules[f] for f in sorted(closure(v))) for k, v in t4.items()}
     for k, want in anchors.items():
         c2, c4 = cited(t2[k]), cited(t4[k])
         for rng in want:
             assert rng in c2, ("two-lane fragments, phase %d: no citation of lines %d-%d" % ((k,) + rng))
             assert rng in c4, ("evg_step4.inc, phase %d: no citation of lines %d-%d" % ((k,) + rng))
+
+    # every rule is called by both mappings, in the same phases
+    _, r2 = phases(two)
+    _, r4 = phases(four)
+    where2 = {f: {k for k, v in r2.items() if f in closure(v)} for f in rules}
+    where4 = {f: {k for k, v in r4.items() if f in closure(v)} for f in rules}
+    for f in rules:
+        assert where2[f], "step_rules.inc: %s is not called by the two-lane kernel" % f
+        assert where2[f] == where4[f], ("step_rules.inc: %s is called in phases %s (two lanes) / %s (four lanes)" % (f, sorted(where2[f]), sorted(where4[f])))
+
+    # the rule formulas are written in the header only: a re-introduced copy in any other device source fails here
+    formulas = {r"\)\s*/\s*denom\b": "the IEEE damage quotient (server.py:601)",
+                r"__builtin_fma\s*\(": "the fast damage quotient",
+                r"0x0C0C0C00": "the damage-byte selection by rank",
+                r"/\s*\(double\)\s*alive\b": "the average-health truncation (:491)",
+                r">=\s*-12\b": "the order id domain (Python-list negative indices)",
+                r"MODE_READY\s*<<\s*G_MODE_S": "the ordered group word (:267-270)",
+                r"\babs\s*\(\s*cs2\s*\)": "the capture threshold (:763-765)",
+                r"\bEVG_(TIME_EXPIRED|ANNIHILATION|BASE_CAPTURE)\b": "the status precedence (:321-328)",
+                r"\bEVG_MAX_SCORE\b": "the reward scaling (everglades_env.py:63-64)"}
+    assert all(re.search(p, strip_comments(rules_src)) for p in formulas), [p for p in formulas if not re.search(p, strip_comments(rules_src))]
+    others = [f for f in os.listdir(csrc) if (f.endswith((".inc", ".h")) or f == "evg_kernels.hip") and f != "step_rules.inc"]
+    assert {"evg_step4.inc", "step_combat.inc", "step_orders.inc", "step_move_capture.inc", "step_outputs.inc"} <= set(others)
+    for f in others:
+        code = strip_comments(open(os.path.join(csrc, f)).read())
+        for p, what in formulas.items():
+            assert not re.search(p, code), "%s: %s is written outside step_rules.inc" % (f, what)
 
 
 def test_kernel_source_hash_is_about_code_not_comments(evg, tmp_path):
