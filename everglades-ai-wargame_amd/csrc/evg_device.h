@@ -148,6 +148,13 @@ struct StepIO {
     int32_t   grid_slots;        // workgroups of a chunked launch (what the device holds at once)
     uint32_t  progress_base;     // value of DevState::progress[set] that means "no chunk of this launch finished yet" (0: the flags are zeroed before
                                  // every launch)
+    const float* q;              // non-NULL: the Q form of the SEAT instantiation (evg_step_vs_policy_smart_q) -- the caller's 7 rows are decoded in the launch
+                                 // from its network output q [N][12][5] (DQNAgent.get_action: coin eps / eps_env, then get_random_actions / get_best_actions)
+    float     eps;
+    const float* eps_env;        // [N] or NULL
+    int32_t*  q_actions;         // [N][7][2] or NULL: the rows played (evg_smart_get_action's actions_out)
+    int32_t*  q_directions;      // [N][7][2] or NULL: {swarm, direction}
+    uint8_t*  q_explored;        // [N] or NULL: 1 where the random branch ran
 #ifdef EVG_DIAG                  // diagnostic libraries only (libevg_diag.so, libevg_stamps.so)
     int32_t   lanes_per_wave;    // 64: 32 envs per wavefront; 32: 16 envs per wavefront + 32 helper lanes
     uint32_t  ablate;            // bit0 orders, bit1 combat, bit2 movement, bit4 obs write-out, bit5 state store

@@ -64,6 +64,7 @@ namespace evg {
 #include "step_common.inc"      // LDS layout of a wavefront's envs, phase fence, sorting network, small device helpers
 #include "step_rules.inc"       // the rules of a turn, written once for both lane mappings (pure register functions)
 #include "step_agents.inc"      // the scripted opponents (one device function over a view)
+#include "smart_decode.inc"     // the Smart_State agent's decode of its Q values (the standalone kernel and the step kernel's Q form)
 #include "step_kernel.inc"      // evg_step_kernel: skeleton + the phases of a turn (step_orders / step_combat / step_move_capture / step_outputs .inc)
 
 #include "evg_step4.inc"        // the four-lanes-per-env mapping: what persistent launches of SMALL batches run (launch_step)
@@ -314,7 +315,7 @@ int launch_step(const DevState& S, const StepIO& io_in, int obs_dtype, const Dev
     return 0;
 }
 
-// evg_step_vs_policy / evg_observe_seat: one launch of the one-seat instantiation of the single-turn two-lane kernel
+// evg_step_vs_policy(_smart / _smart_q) / evg_observe_seat: one launch of the one-seat instantiation of the single-turn two-lane kernel (io.q: its Q form)
 int launch_step_seat(const DevState& S, const StepIO& io_in, int obs_dtype, const DeviceCaps& caps, void* stream) {
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
     if (S.mt_key) return -1;
@@ -324,6 +325,15 @@ int launch_step_seat(const DevState& S, const StepIO& io_in, int obs_dtype, cons
     if (grid2 <= caps.slots2) io.flags |= STEP_F_STAGGER;
     const dim3 grid(grid2), block(WG);
     const StepArgs args{S, io};
+    if (io.q) {              // the Q form (evg_step_vs_policy_smart_q): an instantiation of its own
+        switch (obs_dtype) {
+            case EVG_OBS_F32: hipLaunchKernelGGL((evg_step_kernel<float, WG, false, false, false, true, 1, true>), grid, block, 0, s, args); break;
+            case EVG_OBS_F64: hipLaunchKernelGGL((evg_step_kernel<double, WG, false, false, false, true, 1, true>), grid, block, 0, s, args); break;
+            case EVG_OBS_I16: hipLaunchKernelGGL((evg_step_kernel<int16_t, WG, false, false, false, true, 1, true>), grid, block, 0, s, args); break;
+            default: return -1;
+        }
+        return (int)hipGetLastError();
+    }
     switch (obs_dtype) {
         case EVG_OBS_F32: hipLaunchKernelGGL((evg_step_kernel<float, WG, false, false, false, true>), grid, block, 0, s, args); break;
         case EVG_OBS_F64: hipLaunchKernelGGL((evg_step_kernel<double, WG, false, false, false, true>), grid, block, 0, s, args); break;

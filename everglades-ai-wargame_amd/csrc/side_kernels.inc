@@ -321,7 +321,7 @@ __global__ void __launch_bounds__(256) evg_smart_state_kernel(int N, int player,
 // Mapping: one DPP row (16 lanes) per env, lane = swarm (12 active); a swarm's rank in the stable sort is the number of swarms that come before
 // it, counted over the 15 rotations of the row (key and swarm id travel together, so nothing depends on the direction of the rotation).
 // ---------------------------------------------------------------------------------------------
-#define EVG_ROW_ROTATIONS(X) X(1) X(2) X(3) X(4) X(5) X(6) X(7) X(8) X(9) X(10) X(11) X(12) X(13) X(14) X(15)
+// (the rules themselves -- first maximum, get_move, the rank, the explore draws -- are smart_decode.inc's, shared with the step kernel's Q form)
 //
 // EXPLORE = true is DQNAgent.get_action (:130-146) as a whole: the epsilon coin `random.random() < self.epsilon`, then get_random_actions (:148-173) --
 // swarms = np.random.choice(12, 7, replace=False), directions = np.random.choice(5, 7, replace=True), row i = [swarms[i], get_move(location of swarms[i],
@@ -354,20 +354,10 @@ __global__ void __launch_bounds__(EXPLORE ? 1024 : 256) evg_smart_actions_kernel
             const uint32_t env_id = X.env_id_base + (uint32_t)ed, episode = X.episode[ed];
             const uint4 b0 = rng_block(X.seed_lo, X.seed_hi, env_id, episode, RNG_EXPLORE, 0u, turn, 0, X.seat, 0);
             const uint4 b1 = rng_block(X.seed_lo, X.seed_hi, env_id, episode, RNG_EXPLORE, 1u, turn, 0, X.seat, 0);
-            const uint32_t w0[4] = {b0.x, b0.y, b0.z, b0.w}, w1[4] = {b1.x, b1.y, b1.z, b1.w};
-            const uint32_t coin = (rng_half(w0, 7) << 16) | rng_half(w1, 7);
-            const float eps = X.eps_env ? X.eps_env[ed] : X.eps;
-            const bool explore = (double)coin * (1.0 / 4294967296.0) < (double)eps;           // random.random() < self.epsilon (:140-141), exact in float64
-            if (X.explored) X.explored[ed] = explore ? 1 : 0;
-            uint64_t pool = 0xBA9876543210ull;
-            uint32_t swarms = 0, dirs = 0;
-#pragma unroll
-            for (int i = 0; i < NA; ++i) {
-                swarms |= fy_draw(pool, rng_half(w0, i), (uint32_t)(12 - i)) << (4 * i);      // swarms[i] (:157)
-                dirs |= ((rng_half(w1, i) * 5u) >> 16) << (3 * i);                            // directions[i] (:159)
-            }
-            draws[threadIdx.x][0] = (explore ? 0x80000000u : 0u) | dirs;
-            draws[threadIdx.x][1] = swarms;
+            const uint2 d = smart_explore_words(b0, b1, X.eps_env ? X.eps_env[ed] : X.eps);
+            if (X.explored) X.explored[ed] = (d.x >> 31) ? 1 : 0;
+            draws[threadIdx.x][0] = d.x;
+            draws[threadIdx.x][1] = d.y;
         }
         __syncthreads();
     }
@@ -379,42 +369,18 @@ __global__ void __launch_bounds__(EXPLORE ? 1024 : 256) evg_smart_actions_kernel
         float v[5];
 #pragma unroll
         for (int k = 0; k < 5; ++k) v[k] = qs[k];
-        float best = v[0];
-#pragma unroll
-        for (int k = 1; k < 5; ++k) {                       // torch.argmax / torch.max (:253, :260): first maximum; a NaN is the maximum (torch's rule)
-            const bool take = v[k] > best || (v[k] != v[k] && best == best);
-            dir = take ? k : dir;
-            best = take ? v[k] : best;
-        }
-        key = best != best ? __int_as_float(0x7F800000) : best;     // (a NaN key has no place in the reference's sort: counted as +inf here)
+        key = smart_best(v, dir);
         const OT* o = obs + (seat_only ? (size_t)e : (size_t)e * 2 + player) * OBS;
         const int loc = (int)o[45 + 5 * s];                 // get_swarm_node_number (+ 1): the swarm's node in the player's own numbering
-        // Move_Translation.py:3-82 as nibble tables: nibble n = node reached from node n (left, right, up, down, stay)
-        const uint64_t tab = dir == 0 ? 0xB7654321311ull << 4 : dir == 1 ? 0xBB9BA987651ull << 4 : dir == 2 ? 0x89887653222ull << 4
-                           : dir == 3 ? 0xAAA97654434ull << 4 : 0xBA987654321ull << 4;
-        node = (loc >= 1 && loc <= NN) ? (int)((tab >> (4 * loc)) & 15ull) : 0;      // (an observation without a valid location: node 0, an invalid order)
+        node = smart_move(loc, dir);
         loc_mine = loc;
     }
-    int rank = 0;
-    const int kbits = __float_as_int(key);
-#define EVG_COUNT_BEFORE(R)                                                                                          \
-    {                                                                                                                \
-        const float ko = __int_as_float(__builtin_amdgcn_update_dpp(0, kbits, 0x120 + R, 0xF, 0xF, false));          \
-        const int io_ = __builtin_amdgcn_update_dpp(0, s, 0x120 + R, 0xF, 0xF, false);                                \
-        rank += (ko < key || (ko == key && io_ < s)) ? 1 : 0;                                                         \
-    }
-    EVG_ROW_ROTATIONS(EVG_COUNT_BEFORE)
-#undef EVG_COUNT_BEFORE
+    int rank = smart_rank(key, s);
     if constexpr (EXPLORE) {
-        const uint32_t d0 = draws[threadIdx.x >> 4][0], d1 = draws[threadIdx.x >> 4][1];
-        if (e < N && (d0 >> 31)) {                                                            // get_random_actions (:148-173)
-            rank = NA;                                                                        // not among the seven swarms drawn
-#pragma unroll
-            for (int i = 0; i < NA; ++i)
-                if ((int)((d1 >> (4 * i)) & 15u) == s) { rank = i; dir = (int)((d0 >> (3 * i)) & 7u); }
-            const uint64_t tab = dir == 0 ? 0xB7654321311ull << 4 : dir == 1 ? 0xBB9BA987651ull << 4 : dir == 2 ? 0x89887653222ull << 4
-                               : dir == 3 ? 0xAAA97654434ull << 4 : 0xBA987654321ull << 4;
-            node = (loc_mine >= 1 && loc_mine <= NN) ? (int)((tab >> (4 * loc_mine)) & 15ull) : 0;        // get_move(get_swarm_node_number, direction) (:162-163)
+        const uint2 d = make_uint2(draws[threadIdx.x >> 4][0], draws[threadIdx.x >> 4][1]);
+        if (e < N && (d.x >> 31)) {                                                           // get_random_actions (:148-173)
+            rank = smart_explore_rank(d, s, dir);                                             // NA: not among the seven swarms drawn
+            node = smart_move(loc_mine, dir);                                                 // get_move(get_swarm_node_number, direction) (:162-163)
         }
     }
     if (act && rank < NA) {                                 // sorted_swarm_decisions[:7] (:195-196) / final_action_array (:166-171)
@@ -422,4 +388,3 @@ __global__ void __launch_bounds__(EXPLORE ? 1024 : 256) evg_smart_actions_kernel
         if (directions) directions[(size_t)e * NA + rank] = make_int2(s, dir);
     }
 }
-#undef EVG_ROW_ROTATIONS

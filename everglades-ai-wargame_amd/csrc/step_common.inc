@@ -14,6 +14,15 @@ struct CombatLds {
     uint32_t DP[DP_CAP];                 // damage pool: one byte per targeted unit index, filled with LDS atomics
 };
 
+// The Q form of the one-seat kernel (evg_step_vs_policy_smart_q), prologue only: the wave's network output and the rows decoded from it
+template <int EPW>
+struct SmartQLds {
+    float q[EPW][NG * 5];                // Q values [env][swarm * 5 + direction], as the caller's tensor holds them
+    uint2 draws[EPW];                    // smart_explore_words of each env's agent call
+    int2  rows[EPW][NA];                 // {swarm, node}: the caller's orders
+    int2  dirs[EPW][NA];                 // {swarm, direction}
+};
+
 template <int LPW>
 struct __align__(16) StepLds {
     uint32_t G[12][LPW];                 // group words, lane-private columns (lane = env slot, player)
@@ -22,6 +31,7 @@ struct __align__(16) StepLds {
         CombatLds<LPW> c;
         uint32_t A[12][LPW];             // per (own side, node): capture points | units listed << 16
         int16_t  O[LPW * OBS];           // observations of the wave's envs, already in output order [env][player][105]
+        SmartQLds<LPW / 2> sq;           // (Q form, before the turn's first phase)
     } u;
     LdsTables tab;                       // the per-lane-indexed constant tables (evg_device.h), copied from DevTables::lds
 };

@@ -28,12 +28,16 @@ typedef const StepArgs __attribute__((address_space(4))) * step_args_ptr;
 // WPB (diagnostic library only; round-5 experiment, profiles/r05_*_single_turn_wg256.txt): wavefronts per WORKGROUP of a single-turn launch.  1 is the
 // product's form (one wavefront per workgroup); 4 packs four INDEPENDENT wavefronts -- each with its own StepLds slice and its own 32 envs, still no
 // s_barrier anywhere -- into a 256-thread workgroup, so that a 65 536-env launch is 512 workgroup dispatches instead of 2 048.
-template <typename OT, int LPW, bool MULTI, bool MT = false, bool CHUNKED = false, bool SEAT = false, int WPB = 1>
+// QDEC (evg_step_vs_policy_smart_q): the Q form of SEAT -- the caller hands its network output instead of its orders, and the launch decodes the 7 rows
+// (DQNAgent.get_action: the epsilon coin, get_random_actions / get_best_actions; smart_decode.inc) in its prologue, over the whole wavefront: the order rows
+// never go through HBM and the learner's turn is one launch from the network's output to its next input.
+template <typename OT, int LPW, bool MULTI, bool MT = false, bool CHUNKED = false, bool SEAT = false, int WPB = 1, bool QDEC = false>
 __global__ void __launch_bounds__(WG * WPB) __attribute__((amdgpu_waves_per_eu(2, 2))) evg_step_kernel(StepArgs) {
     static_assert(!MT || (!MULTI && LPW == WG), "the stock-entropy mode exists in the single-turn, 32-envs-per-wave form only");
     static_assert(!CHUNKED || (MULTI && LPW == WG && !MT), "the chunked form is an instantiation of the persistent two-lane kernel");
     static_assert(!SEAT || (!MULTI && !MT && LPW == WG), "the one-seat form is an instantiation of the single-turn two-lane kernel");
     static_assert(WPB == 1 || (!MULTI && !MT && !CHUNKED && !SEAT && LPW == WG), "several wavefronts per workgroup: the plain single-turn two-lane form only");
+    static_assert(!QDEC || (SEAT && WPB == 1), "the Q form is an instantiation of the one-seat kernel");
     step_args_ptr A = (step_args_ptr)__builtin_amdgcn_kernarg_segment_ptr();
     constexpr int EPW = LPW / 2;                        // envs per wavefront
     constexpr int DP_CAP = CombatLds<LPW>::DP_CAP;
@@ -150,16 +154,32 @@ __global__ void __launch_bounds__(WG * WPB) __attribute__((amdgpu_waves_per_eu(2
     int2 act_in[NA];
 #pragma unroll
     for (int i = 0; i < NA; ++i) act_in[i] = make_int2(0, 0);
-    if constexpr (SEAT) {                               // the caller's seat: [N][7][2], or its rows of a [N][2][7][2] tensor
+    if constexpr (SEAT && !QDEC) {                      // the caller's seat: [N][7][2], or its rows of a [N][2][7][2] tensor
         if (io.actions && P == io.seat) {
             const int2* ap = reinterpret_cast<const int2*>(io.actions) + (io.actions_both ? ((size_t)e * 2 + P) * NA : (size_t)e * NA);
 #pragma unroll
             for (int i = 0; i < NA; ++i) act_in[i] = ap[i];
         }
-    } else if (!MULTI && !io.gen_actions && io.actions) {
+    } else if (!MULTI && !SEAT && !io.gen_actions && io.actions) {
         const int2* ap = reinterpret_cast<const int2*>(io.actions) + ((size_t)e * 2 + P) * NA;
 #pragma unroll
         for (int i = 0; i < NA; ++i) act_in[i] = ap[i];
+    }
+    // Q form: the caller's network output for the wave's envs -- 240 contiguous bytes each, 16 bytes per lane -- and its epsilon are part of the same round trip
+    constexpr int QV = QDEC ? (EPW * NG * 5 / 4 + WG - 1) / WG : 1;              // 16-byte pieces per lane (480 per wave: 8)
+    [[maybe_unused]] uint4 qv[QV];
+    [[maybe_unused]] float eps_q = 0.f;
+    [[maybe_unused]] uint2 qdraw = make_uint2(0u, 0u);
+    if constexpr (QDEC) {
+        static_assert(NG * 5 % 4 == 0, "an env's Q values are a whole number of 16-byte pieces");
+        const uint4* qs = reinterpret_cast<const uint4*>(io.q) + (size_t)e0 * (NG * 5 / 4);      // 16-byte aligned (checked by the entry point)
+        const int nq = nvalid * (NG * 5 / 4);
+#pragma unroll
+        for (int i = 0; i < QV; ++i) {
+            const int v = lane + WG * i;
+            qv[i] = v < nq ? qs[v] : make_uint4(0u, 0u, 0u, 0u);
+        }
+        eps_q = io.eps_env ? io.eps_env[e] : io.eps;
     }
     int turn = (int)(envw & 0xFFu);
     int status = (int)((envw >> 8) & 3u);
@@ -190,6 +210,13 @@ __global__ void __launch_bounds__(WG * WPB) __attribute__((amdgpu_waves_per_eu(2
         // ... and the orders this kernel draws itself need only the turn and the episode (the first two loads), so they are
         // drawn while the group / node words are still on their way
         if (io.gen_actions == 1) gen_random_rows(S.seed_lo, S.seed_hi, S.env_id_base + (uint32_t)e, episode, turn, P, act_in);
+        if constexpr (QDEC) {
+            // the caller's agent call draws two Philox blocks (smart_decode.inc): each lane of the pair draws one -- block P -- and the pair swaps them
+            // (DPP), so that both lanes hold the env's coin and draws, no lane idles behind its partner
+            const uint4 b = rng_block(S.seed_lo, S.seed_hi, S.env_id_base + (uint32_t)e, episode, RNG_EXPLORE, (uint32_t)P, turn, 0, io.seat, 0);
+            const uint4 o = make_uint4((uint32_t)xchg1((int)b.x), (uint32_t)xchg1((int)b.y), (uint32_t)xchg1((int)b.z), (uint32_t)xchg1((int)b.w));
+            qdraw = smart_explore_words(P ? o : b, P ? b : o, eps_q);
+        }
     }
     {
         uint4* lt = reinterpret_cast<uint4*>(&L.tab);
@@ -205,11 +232,73 @@ __global__ void __launch_bounds__(WG * WPB) __attribute__((amdgpu_waves_per_eu(2
             if (n <= NN) L.NW[n][E] = (n_in[j >> 1] >> (16 * (j & 1))) & 0xFFFFu;
         }
     }
+    if constexpr (QDEC) {
+        uint4* ql = reinterpret_cast<uint4*>(&L.u.sq.q[0][0]);
+#pragma unroll
+        for (int i = 0; i < QV; ++i)
+            if (lane + WG * i < EPW * NG * 5 / 4) ql[lane + WG * i] = qv[i];
+        if (P == 0) L.u.sq.draws[E] = qdraw;
+    }
     WAVE_SYNC();
     // Every prologue load is waited for here, before the turn loop: a register whose load may still be in flight on SOME path
     // makes the compiler put s_waitcnt vmcnt(0) in front of its first use inside the loop, where it would wait for the previous
     // turn's observation stores on every turn.
     asm volatile("" :: "v"(episode), "v"(ep_ret), "v"(ag_cycle), "v"(ag_swarm), "v"(ag_dfs));
+    if constexpr (QDEC) {
+        // ---- Q form: the caller's 7 rows from its network output (DQNAgent.get_action, agents/Smart_State/DQNAgent.py:130-198), the whole wavefront at
+        // once -- one DPP row (16 lanes) per env, lane = swarm, four envs per pass -- with the rules of evg_smart_actions_kernel (smart_decode.inc).  The
+        // swarm's location is its group word's (the state this launch starts from is what the previous launch's observation shows: with auto_reset a
+        // finished env's observation is the first of its next episode), in the caller's own numbering: what obs[45 + 5 s] holds.  Rows of every valid env
+        // are decoded and written out, frozen ones included, as evg_smart_get_action writes every env.
+        const int sw = lane & 15, sub = lane >> 4;
+        const uint64_t own_q = player_node_map(io.seat, L.tab.nib[0]);
+        for (int ps = 0; ps < EPW / 4; ++ps) {
+            const int ep = 4 * ps + sub;                  // env slot of this lane's row
+            const bool act = sw < NG && ep < nvalid;
+            float key = __int_as_float(0x7F800000);      // idle lanes: +inf with ids 12..15, never in front of a swarm
+            int dir = 0, node = 0, loc = 0;
+            if (act) {
+                float v[5];
+#pragma unroll
+                for (int k = 0; k < 5; ++k) v[k] = L.u.sq.q[ep][5 * sw + k];
+                key = smart_best(v, dir);
+                loc = (int)map_node(own_q, L.G[sw][2 * ep + io.seat] & G_LOC_M);
+                node = smart_move(loc, dir);
+            }
+            int rank = smart_rank(key, sw);
+            const uint2 d = L.u.sq.draws[ep];
+            if (ep < nvalid && (d.x >> 31)) {            // get_random_actions
+                rank = smart_explore_rank(d, sw, dir);
+                node = smart_move(loc, dir);
+            }
+            if (act && rank < NA) {
+                L.u.sq.rows[ep][rank] = make_int2(sw, node);
+                L.u.sq.dirs[ep][rank] = make_int2(sw, dir);
+            }
+        }
+        WAVE_SYNC();
+        if (P == io.seat) {
+#pragma unroll
+            for (int i = 0; i < NA; ++i) act_in[i] = L.u.sq.rows[E][i];
+        }
+        if (valid && P == 0 && io.q_explored) io.q_explored[e] = (uint8_t)(qdraw.x >> 31);
+        // rows played and directions: the wave's rows are contiguous in [N][7][2] (e0 * 56 bytes: 16-byte aligned), stored 16 bytes per lane
+        auto put_rows = [&](int32_t* out, const int2* src) {
+            int2* dst = reinterpret_cast<int2*>(out) + (size_t)e0 * NA;
+            if (nvalid == EPW) {
+#pragma unroll
+                for (int i = 0; i < (EPW * NA / 2 + WG - 1) / WG; ++i) {
+                    const int v = lane + WG * i;
+                    if (v < EPW * NA / 2) reinterpret_cast<uint4*>(dst)[v] = reinterpret_cast<const uint4*>(src)[v];
+                }
+            } else {
+                for (int v = lane; v < nvalid * NA; v += WG) dst[v] = src[v];      // last, partial workgroup of the grid
+            }
+        };
+        if (io.q_actions) put_rows(io.q_actions, &L.u.sq.rows[0][0]);
+        if (io.q_directions) put_rows(io.q_directions, &L.u.sq.dirs[0][0]);
+        WAVE_SYNC();                                      // the union is the turn's scratch from here on
+    }
     const bool observe_only = io.observe_only != 0;
     // stock-entropy mode: the env's MT19937 is advanced by the lane of player 0, in the reference's draw order
     MtGen mt{nullptr, 0, 0};

@@ -241,6 +241,42 @@ class EvergladesVecEnv(object):
             self._check(rc)
         return obs, self.reward, self.done, self._info
 
+    def step_vs_q(self, policy, q, epsilon, seat=0, features=None, directions=None, explored=None, actions_out=None, out=None):
+        """The Smart_State learner's turn from its Q values, in ONE launch (evg_step_vs_policy_smart_q): DQNAgent.get_action for `seat` -- the epsilon
+        coin, then get_random_actions or get_best_actions, as smart_get_action() -- then step_vs(policy) with those rows.  `q` float32 [N, 12, 5]: the
+        network's output; `epsilon` a float in [0, 1] or a float32 tensor [N].  Returns (obs_seat [N, 105], reward [N, 2], done [N], info) like step_vs();
+        bit-identical to smart_get_action(q, epsilon, seat, obs=<the previous seat observation>) + step_vs(policy, rows, seat).  features=(shared [N, 34],
+        swarm [N, 12, 13]) as in step_vs() (shared 16-byte aligned); `directions` / `actions_out` int32 [N, 7, 2] receive {swarm, direction} / the rows
+        played, `explored` uint8 [N] 1 where the random branch ran.  No host synchronisation and no allocation per call: it can sit inside a captured loop."""
+        torch = _torch()
+        pid = self.POLICIES[policy] if isinstance(policy, str) else int(policy)
+        N = self.num_envs
+        self._user(q, (N, _lib.NUM_GROUPS, 5), torch.float32, "q")
+        obs = self._seat_buffers() if out is None else self._user(out, (N, _lib.OBS_LEN), self.obs_dtype, "out")
+        shared = swarm = None
+        if features is not None:
+            shared, swarm = features
+            self._user(shared, (N, 34), torch.float32, "features[0] (shared)")
+            self._user(swarm, (N, _lib.NUM_GROUPS, 13), torch.float32, "features[1] (swarm)")
+        if directions is not None:
+            self._user(directions, (N, _lib.NUM_ACTIONS, 2), self._int32, "directions")
+        if actions_out is not None:
+            self._user(actions_out, (N, _lib.NUM_ACTIONS, 2), self._int32, "actions_out")
+        if explored is not None:
+            self._user(explored, (N,), torch.uint8, "explored")
+        eps_env = None
+        if isinstance(epsilon, torch.Tensor):
+            eps_env = self._user(epsilon, (N,), torch.float32, "epsilon")
+            epsilon = 0.0
+        p = self._p
+        rc = self.L.evg_step_vs_policy_smart_q(self._h, int(seat), C.c_void_p(q.data_ptr()), float(epsilon), self._ptr(eps_env), pid,
+                                               C.c_void_p(obs.data_ptr()), self._ptr(shared), self._ptr(swarm), self._ptr(actions_out),
+                                               self._ptr(directions), self._ptr(explored), p["reward"], p["done"], p["winner"], p["scores"], p["status"],
+                                               self._stream())
+        if rc:
+            self._check(rc)
+        return obs, self.reward, self.done, self._info
+
     def rollout_vs(self, steps, policy, seat=0, time_kernel=False):
         """`steps` turns of the learner-seat loop driven from native code (evg_rollout_vs_policy): per turn the on-device random_actions
         generator writes the caller seat's rows into a tensor (the stand-in for a policy network's output), then step_vs(policy) runs.

@@ -6,10 +6,12 @@ with everything but the network on the device, one launch each:
              --evg_smart_get_action (epsilon coin, get_random_actions / get_best_actions)--> orders [N, 7, 2] (+ directions for the replay memory)
              --evg_step_vs_policy_smart (the scripted opponent inside the step kernel)--> observation, reward, done AND the next features
 
+or, with fused=True, the last two as one launch from Q to the next features (evg_step_vs_policy_smart_q: the orders never go through HBM).
+
 The network here is a stand-in with random weights, evaluated on the COMPACT features: features[e, s] = cat(shared[e], swarm[e, s], onehot(s)), so the first
 layer is W[:, :34] @ shared + W[:, 34:47] @ swarm + W[:, 47 + s] -- a quarter of the bytes of the expanded [N, 12, 59] matrix.
 
-    python examples/smart_state_loop.py [envs] [turns] [epsilon]
+    python examples/smart_state_loop.py [envs] [turns] [epsilon] [fused]
 """
 import os
 import sys
@@ -36,7 +38,7 @@ def make_network(device, seed=0):
     return q_values
 
 
-def main(num_envs=8192, turns=200, epsilon=0.1, opponent="swarm_agent", seat=0, seed=1):
+def main(num_envs=8192, turns=200, epsilon=0.1, opponent="swarm_agent", seat=0, seed=1, fused=False):
     env = evg.EvergladesVecEnv(num_envs, seed=seed, auto_reset=True)
     net = make_network(env.device)
     env.reset()
@@ -48,8 +50,11 @@ def main(num_envs=8192, turns=200, epsilon=0.1, opponent="swarm_agent", seat=0, 
     t0, ret = time.perf_counter(), torch.zeros((num_envs, 2), device=env.device)
     for _ in range(turns):
         q = net(shared, swarm)
-        actions = env.smart_get_action(q, epsilon, seat=seat, obs=obs, directions=directions, explored=explored)
-        obs, reward, done, info = env.step_vs(opponent, actions, seat=seat, features=(shared, swarm))
+        if fused:            # one launch: the orders are decoded from q inside the step (evg_step_vs_policy_smart_q)
+            obs, reward, done, info = env.step_vs_q(opponent, q, epsilon, seat=seat, features=(shared, swarm), directions=directions, explored=explored)
+        else:
+            actions = env.smart_get_action(q, epsilon, seat=seat, obs=obs, directions=directions, explored=explored)
+            obs, reward, done, info = env.step_vs(opponent, actions, seat=seat, features=(shared, swarm))
         ret += reward                                                  # (a learner would push (features, directions, reward, done) into its replay memory here)
     torch.cuda.synchronize()
     dt = time.perf_counter() - t0
@@ -62,4 +67,4 @@ def main(num_envs=8192, turns=200, epsilon=0.1, opponent="swarm_agent", seat=0, 
 
 if __name__ == "__main__":
     a = sys.argv[1:]
-    main(int(a[0]) if a else 8192, int(a[1]) if len(a) > 1 else 200, float(a[2]) if len(a) > 2 else 0.1)
+    main(int(a[0]) if a else 8192, int(a[1]) if len(a) > 1 else 200, float(a[2]) if len(a) > 2 else 0.1, fused=len(a) > 3 and a[3] in ("1", "fused"))

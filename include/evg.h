@@ -36,7 +36,8 @@
 extern "C" {
 #endif
 
-#define EVG_ABI_VERSION 6
+#define EVG_ABI_VERSION 7
+/* 7: evg_step_vs_policy_smart_q (the Smart_State learner's turn from its Q values: DQNAgent.get_action decoded inside the learner-seat step launch) */
 /* 6: evg_smart_get_action (DQNAgent.get_action with epsilon > 0), evg_step_vs_policy_smart (the learner-seat turn that also writes the Smart_State
  *    features), evg_get_run_state / evg_set_run_state (agent objects, returns, win counters: checkpoint / resume); reward / score buffers need 8-byte
  *    alignment only (5 asked 16 of every buffer)
@@ -208,6 +209,29 @@ EVG_API int evg_step_vs_policy(evg_handle* h, int seat, const int32_t* actions, 
 EVG_API int evg_step_vs_policy_smart(evg_handle* h, int seat, const int32_t* actions, int actions_both_seats, int opponent_policy, void* obs_seat_out,
                                      float* shared_out, float* swarm_out, float* reward_out, uint8_t* done_out, int8_t* winner_out, int32_t* scores_out,
                                      uint8_t* status_out, void* stream);
+/* The Smart_State learner's whole turn in ONE launch, from its network's output to its network's next input
+ * (agents/Smart_State/training_scripts/dqn_smart_state_training.py:114-122): the caller hands its Q values, not its orders.  The launch does
+ * DQNAgent.get_action for the caller's seat -- the epsilon coin, then get_random_actions or get_best_actions, exactly as evg_smart_get_action -- plays the
+ * scripted opponent, steps the game and writes the next observation and (optionally) the compact features, as evg_step_vs_policy_smart.  The order rows
+ * never go through HBM unless asked for.
+ *   seat             0 or 1: the caller's seat (also the agent's player number that keys its draws)
+ *   q                device float [N][12][5] (16-byte aligned): the network's Q values of every swarm; domain as in evg_smart_actions (first maximum,
+ *                    a NaN is the maximum and sorts like +inf, stable ascending sort, first seven)
+ *   epsilon, epsilon_env  as in evg_smart_get_action (epsilon must lie in [0, 1] when epsilon_env is NULL)
+ *   opponent_policy, obs_seat_out, reward_out, done_out, winner_out, scores_out, status_out: as in evg_step_vs_policy
+ *   shared_out, swarm_out  both NULL or both set: the features of evg_step_vs_policy_smart; here shared_out must be 16-byte aligned
+ *   actions_out      device int32 [N][7][2] or NULL: the rows the caller's seat played ({swarm, node})
+ *   directions_out   device int32 [N][7][2] or NULL: {swarm, direction} (what the reference's replay memory stores)
+ *   explored_out     device uint8 [N] or NULL: 1 where the random branch ran
+ * The decode reads each swarm's location, the turn and the episode from the state the launch starts from: what the seat observation of the previous
+ * launch (or evg_observe_seat) shows, also across auto-resets.  Results -- every output above, and the handle's state afterwards -- are bit for bit those
+ * of evg_smart_get_action(h, seat, 1, obs_prev, q, epsilon, epsilon_env, a, d, x) followed by evg_step_vs_policy_smart(h, seat, a, 0, ...) (or
+ * evg_step_vs_policy), with obs_prev the seat observation of the previous launch.  Every env's rows, directions and explored flag are written, finished
+ * ones included (as evg_smart_get_action does).  Keyed-Philox handles only. */
+EVG_API int evg_step_vs_policy_smart_q(evg_handle* h, int seat, const float* q, float epsilon, const float* epsilon_env, int opponent_policy,
+                                       void* obs_seat_out, float* shared_out, float* swarm_out,
+                                       int32_t* actions_out, int32_t* directions_out, uint8_t* explored_out,
+                                       float* reward_out, uint8_t* done_out, int8_t* winner_out, int32_t* scores_out, uint8_t* status_out, void* stream);
 /* evg_observe for one seat: obs_seat_out device [N][105] (after evg_reset / evg_set_state, to start a evg_step_vs_policy loop). */
 EVG_API int evg_observe_seat(evg_handle* h, int seat, void* obs_seat_out, void* stream);
 
