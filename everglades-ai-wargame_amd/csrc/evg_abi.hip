@@ -713,6 +713,28 @@ int evg_step_vs_policy_smart_q(evg_handle* h, int seat, const float* q, float ep
     return EVG_OK;
 } catch (...) { return on_exception(); }
 
+int evg_step_smart_q(evg_handle* h, const float* q, float epsilon0, float epsilon1, const float* epsilon_env, void* obs_out, float* shared_out, float* swarm_out,
+                     int32_t* actions_out, int32_t* directions_out, uint8_t* explored_out, float* reward_out, uint8_t* done_out, int8_t* winner_out,
+                     int32_t* scores_out, uint8_t* status_out, void* stream) try {
+    if (!h) return fail(EVG_ERR_INVALID, "null handle");
+    if (!q || !obs_out || !reward_out || !done_out) return fail(EVG_ERR_INVALID, "q, obs_out, reward_out and done_out are required");
+    if (!epsilon_env && !(epsilon0 >= 0.0f && epsilon0 <= 1.0f && epsilon1 >= 0.0f && epsilon1 <= 1.0f))
+        return fail(EVG_ERR_INVALID, "epsilon0 %g / epsilon1 %g outside [0, 1]", (double)epsilon0, (double)epsilon1);
+    if (!shared_out != !swarm_out) return fail(EVG_ERR_INVALID, "shared_out and swarm_out are both NULL or both set");
+    // (the fused feature store writes shared_out and swarm_out as float4)
+    EVG_NEED_ALIGNED16(q); EVG_NEED_ALIGNED16(obs_out); EVG_NEED_ALIGNED16(shared_out); EVG_NEED_ALIGNED16(swarm_out);
+    EVG_NEED_ALIGNED16(actions_out); EVG_NEED_ALIGNED16(directions_out); EVG_NEED_ALIGNED8(reward_out); EVG_NEED_ALIGNED8(scores_out);
+    if (h->S.mt_key) return fail(EVG_ERR_INVALID, "evg_step_smart_q: keyed-Philox handles only (the stock-entropy mode has no fused decode)");
+    EVG_ON_DEVICE(h);
+    StepIO io = make_io(h, nullptr, obs_out, reward_out, done_out, winner_out, scores_out, status_out, 0, 0, 0, 0, nullptr);
+    io.feat_shared = shared_out; io.feat_swarm = swarm_out;
+    io.q = q; io.eps = epsilon0; io.eps1 = epsilon1; io.eps_env = epsilon_env;
+    io.q_actions = actions_out; io.q_directions = directions_out; io.q_explored = explored_out;
+    const int rc = launch_step_smart_q(h->S, io, h->cfg.obs_dtype, h->caps, stream);
+    if (rc) return fail(EVG_ERR_HIP, "step launch failed: %s", hipGetErrorString((hipError_t)rc));
+    return EVG_OK;
+} catch (...) { return on_exception(); }
+
 int evg_observe_seat(evg_handle* h, int seat, void* obs_seat_out, void* stream) try {
     if (!h || !obs_seat_out || seat < 0 || seat > 1) return fail(EVG_ERR_INVALID, "bad argument");
     EVG_NEED_ALIGNED16(obs_seat_out);

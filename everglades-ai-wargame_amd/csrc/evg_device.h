@@ -140,8 +140,9 @@ struct StepIO {
                                  // or rows [:, seat] of [N][2][7][2] when actions_both != 0), the other seat's from policy0 / policy1 (gen_actions == 2),
                                  // and obs is [N][105]
     int32_t   actions_both;
-    float*    feat_shared;       // SEAT instantiation only (evg_step_vs_policy_smart): non-NULL = also write the Smart_State features of the caller's seat, compact
-    float*    feat_swarm;        // form -- shared [N][34], swarm [N][12][13] (evg_smart_state_compact's outputs) -- straight from the observation image in LDS
+    float*    feat_shared;       // SEAT instantiation (evg_step_vs_policy_smart): non-NULL = also write the Smart_State features of the caller's seat, compact
+    float*    feat_swarm;        // form -- shared [N][34], swarm [N][12][13] (evg_smart_state_compact's outputs) -- straight from the observation image in LDS;
+                                 // two-seat Q form (evg_step_smart_q): both players', shared [N][2][34], swarm [N][2][12][13]
     int32_t   nsets;             // > 0: CHUNKED persistent launch of the two-lane kernel (batches beyond what the device holds at once): workgroup u
                                  // plays chunk u / nsets (chunk_turns consecutive turns, the last one what is left of `turns`) of env set u % nsets
     int32_t   chunk_turns;
@@ -150,11 +151,13 @@ struct StepIO {
                                  // every launch)
     const float* q;              // non-NULL: the Q form of the SEAT instantiation (evg_step_vs_policy_smart_q) -- the caller's 7 rows are decoded in the launch
                                  // from its network output q [N][12][5] (DQNAgent.get_action: coin eps / eps_env, then get_random_actions / get_best_actions)
-    float     eps;
-    const float* eps_env;        // [N] or NULL
-    int32_t*  q_actions;         // [N][7][2] or NULL: the rows played (evg_smart_get_action's actions_out)
-    int32_t*  q_directions;      // [N][7][2] or NULL: {swarm, direction}
-    uint8_t*  q_explored;        // [N] or NULL: 1 where the random branch ran
+                                 // -- or of the plain single-turn kernel (evg_step_smart_q, self-play): both seats' rows from q [N][2][12][5]
+    float     eps;               // (two-seat Q form: seat 0's)
+    float     eps1;              // two-seat Q form: seat 1's epsilon
+    const float* eps_env;        // [N] or NULL (two-seat Q form: [N][2])
+    int32_t*  q_actions;         // [N][7][2] or NULL: the rows played (evg_smart_get_action's actions_out); two-seat Q form: [N][2][7][2]
+    int32_t*  q_directions;      // [N][7][2] or NULL: {swarm, direction}; two-seat Q form: [N][2][7][2]
+    uint8_t*  q_explored;        // [N] or NULL: 1 where the random branch ran; two-seat Q form: [N][2]
 #ifdef EVG_DIAG                  // diagnostic libraries only (libevg_diag.so, libevg_stamps.so)
     int32_t   lanes_per_wave;    // 64: 32 envs per wavefront; 32: 16 envs per wavefront + 32 helper lanes
     uint32_t  ablate;            // bit0 orders, bit1 combat, bit2 movement, bit4 obs write-out, bit5 state store
@@ -191,6 +194,7 @@ LaunchPlan plan_step(const DevState& S, const StepIO& io, int obs_dtype, const D
 long long rollout_bytes_per_env(const StepIO& io, int obs_dtype);
 int launch_step(const DevState& S, const StepIO& io, int obs_dtype, const DeviceCaps& caps, void* stream);
 int launch_step_seat(const DevState& S, const StepIO& io, int obs_dtype, const DeviceCaps& caps, void* stream);
+int launch_step_smart_q(const DevState& S, const StepIO& io, int obs_dtype, const DeviceCaps& caps, void* stream);
 int launch_reset(const DevState& S, const uint8_t* mask, void* obs, int obs_dtype, void* stream);
 int launch_random_actions(const DevState& S, int32_t* actions, int seat /* -1: both, [N][2][7][2]; 0 / 1: that seat only, [N][7][2] */, void* stream);
 int launch_scripted_actions(const DevState& S, int policy, int player, const void* obs, int32_t* actions, int obs_dtype, void* stream);

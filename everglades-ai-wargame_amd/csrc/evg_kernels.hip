@@ -315,6 +315,25 @@ int launch_step(const DevState& S, const StepIO& io_in, int obs_dtype, const Dev
     return 0;
 }
 
+// evg_step_smart_q (self-play): one launch of the two-seat Q form of the single-turn two-lane kernel -- both seats' rows decoded from io.q in the launch
+int launch_step_smart_q(const DevState& S, const StepIO& io_in, int obs_dtype, const DeviceCaps& caps, void* stream) {
+    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+    if (S.mt_key || !io_in.q) return -1;
+    StepIO io = io_in;
+    io.turns = 1; io.env_lo = 0; io.env_hi = S.N; io.flags = 0; io.nsets = 0; io.chunk_turns = 0; io.progress_base = 0; io.grid_slots = 0;
+    const int grid2 = (S.N + WG / 2 - 1) / (WG / 2);
+    if (grid2 <= caps.slots2) io.flags |= STEP_F_STAGGER;
+    const dim3 grid(grid2), block(WG);
+    const StepArgs args{S, io};
+    switch (obs_dtype) {
+        case EVG_OBS_F32: hipLaunchKernelGGL((evg_step_kernel<float, WG, false, false, false, false, 1, true>), grid, block, 0, s, args); break;
+        case EVG_OBS_F64: hipLaunchKernelGGL((evg_step_kernel<double, WG, false, false, false, false, 1, true>), grid, block, 0, s, args); break;
+        case EVG_OBS_I16: hipLaunchKernelGGL((evg_step_kernel<int16_t, WG, false, false, false, false, 1, true>), grid, block, 0, s, args); break;
+        default: return -1;
+    }
+    return (int)hipGetLastError();
+}
+
 // evg_step_vs_policy(_smart / _smart_q) / evg_observe_seat: one launch of the one-seat instantiation of the single-turn two-lane kernel (io.q: its Q form)
 int launch_step_seat(const DevState& S, const StepIO& io_in, int obs_dtype, const DeviceCaps& caps, void* stream) {
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);

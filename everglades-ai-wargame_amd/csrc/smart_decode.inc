@@ -1,7 +1,8 @@
 // smart_decode.inc -- the Smart_State agent's decode of its network output, network output -> 7 order rows (DQNAgent.get_action / get_best_actions /
-// get_random_actions, agents/Smart_State/DQNAgent.py:130-198; Move_Translation.get_move), written once for the two kernels that run it: the standalone
-// evg_smart_actions_kernel (side_kernels.inc) and the learner-seat step kernel's Q form (step_kernel.inc, evg_step_vs_policy_smart_q).
-// Both map one DPP row (16 lanes) to an env, lane = swarm (12 active).  Included by evg_kernels.hip inside namespace evg.
+// get_random_actions, agents/Smart_State/DQNAgent.py:130-198; Move_Translation.get_move), written once for the kernels that run it: the standalone
+// evg_smart_actions_kernel (side_kernels.inc) and the step kernel's Q forms (step_kernel.inc: evg_step_vs_policy_smart_q, one seat; evg_step_smart_q, both).
+// Both map one DPP row (16 lanes) to an env, lane = swarm (12 active).  At the end, the compact features of an observation row, shared by the step kernel's
+// fused forms.  Included by evg_kernels.hip inside namespace evg.
 
 // Move_Translation.py:3-82 as nibble tables: nibble n = node reached from node n (left, right, up, down, stay); a location outside 1..11 gives node 0 (an
 // invalid order)
@@ -70,3 +71,28 @@ __device__ __forceinline__ int smart_explore_rank(const uint2 d, int s, int& dir
         if ((int)((d.y >> (4 * i)) & 15u) == s) { rank = i; dir = (int)((d.x >> (3 * i)) & 7u); }
     return rank;
 }
+
+// ---- the agent's next input: the compact Smart_State features of one observation row (DQNAgent.py:200-300; evg_smart_state_compact's values), as the
+// step kernel's fused forms compute them -- the one-seat form (evg_step_vs_policy_smart) from the row in LDS, the two-seat Q form (evg_step_smart_q) from a
+// copy of it in registers.  `r` is anything indexed like the row [105]; every index below is a compile-time constant at each call.  Every quotient is the
+// float64 product with the rounded reciprocal, rounded once to float32: exactly the standalone kernel's arithmetic (side_kernels.inc).
+// nibble n: groups listed at node n (own numbering) that are not in transit (:200-213)
+template <typename R>
+__device__ __forceinline__ uint64_t smart_idle_nibbles(const R& r) {
+    uint64_t idle = 0;
+#pragma unroll
+    for (int k = 0; k < NG; ++k) idle += (uint64_t)(r[48 + 5 * k] == 0 ? 1u : 0u) << (4 * (r[45 + 5 * k] & 15));
+    return idle;
+}
+// shared[j], j < 34: {turn / 150, 11 x control / 100, 11 x opposing units / 100, 11 x idle allied groups / 12} (:280-286)
+template <typename R>
+__device__ __forceinline__ float smart_shared_feature(const R& r, int j, uint64_t idle) {
+    if (j == 0) return (float)((double)r[0] * (1.0 / 150.0));
+    if (j < 12) return (float)((double)r[3 + 4 * (j - 1)] * (1.0 / 100.0));
+    if (j < 23) return (float)((double)r[4 + 4 * (j - 12)] * (1.0 / 100.0));
+    return (float)((double)(int)((idle >> (4 * (j - 22))) & 15ull) * (1.0 / 12.0));
+}
+// swarm[k][f], f < 13: {one-hot node (11), average health x alive / 1000, in transit} (:288-296), from the swarm's location, health term and transit flag
+template <typename R>
+__device__ __forceinline__ float smart_swarm_health(const R& r, int k) { return (float)((double)((int)r[47 + 5 * k] * (int)r[49 + 5 * k]) * (1.0 / 1000.0)); }
+__device__ __forceinline__ float smart_swarm_feature(int loc, float hp, float mov, int f) { return f < NN ? (loc == f + 1 ? 1.f : 0.f) : (f == NN ? hp : mov); }

@@ -31,13 +31,16 @@ typedef const StepArgs __attribute__((address_space(4))) * step_args_ptr;
 // QDEC (evg_step_vs_policy_smart_q): the Q form of SEAT -- the caller hands its network output instead of its orders, and the launch decodes the 7 rows
 // (DQNAgent.get_action: the epsilon coin, get_random_actions / get_best_actions; smart_decode.inc) in its prologue, over the whole wavefront: the order rows
 // never go through HBM and the learner's turn is one launch from the network's output to its next input.
+// QDEC without SEAT (evg_step_smart_q): the Q form of the plain single-turn kernel -- self-play, a DQNAgent on each seat: both seats' rows are decoded in the
+// prologue, one seat per pass through the same LDS (the two seats' Q values, 15 360 B per wave, do not fit the union at once), and both players' features are
+// written after the observation write-out.
 template <typename OT, int LPW, bool MULTI, bool MT = false, bool CHUNKED = false, bool SEAT = false, int WPB = 1, bool QDEC = false>
 __global__ void __launch_bounds__(WG * WPB) __attribute__((amdgpu_waves_per_eu(2, 2))) evg_step_kernel(StepArgs) {
     static_assert(!MT || (!MULTI && LPW == WG), "the stock-entropy mode exists in the single-turn, 32-envs-per-wave form only");
     static_assert(!CHUNKED || (MULTI && LPW == WG && !MT), "the chunked form is an instantiation of the persistent two-lane kernel");
     static_assert(!SEAT || (!MULTI && !MT && LPW == WG), "the one-seat form is an instantiation of the single-turn two-lane kernel");
     static_assert(WPB == 1 || (!MULTI && !MT && !CHUNKED && !SEAT && LPW == WG), "several wavefronts per workgroup: the plain single-turn two-lane form only");
-    static_assert(!QDEC || (SEAT && WPB == 1), "the Q form is an instantiation of the one-seat kernel");
+    static_assert(!QDEC || (!MULTI && !MT && LPW == WG && WPB == 1), "the Q form is an instantiation of the single-turn two-lane kernel (one seat or two)");
     step_args_ptr A = (step_args_ptr)__builtin_amdgcn_kernarg_segment_ptr();
     constexpr int EPW = LPW / 2;                        // envs per wavefront
     constexpr int DP_CAP = CombatLds<LPW>::DP_CAP;
@@ -160,26 +163,42 @@ __global__ void __launch_bounds__(WG * WPB) __attribute__((amdgpu_waves_per_eu(2
 #pragma unroll
             for (int i = 0; i < NA; ++i) act_in[i] = ap[i];
         }
-    } else if (!MULTI && !SEAT && !io.gen_actions && io.actions) {
+    } else if (!MULTI && !SEAT && !QDEC && !io.gen_actions && io.actions) {
         const int2* ap = reinterpret_cast<const int2*>(io.actions) + ((size_t)e * 2 + P) * NA;
 #pragma unroll
         for (int i = 0; i < NA; ++i) act_in[i] = ap[i];
     }
     // Q form: the caller's network output for the wave's envs -- 240 contiguous bytes each, 16 bytes per lane -- and its epsilon are part of the same round trip
-    constexpr int QV = QDEC ? (EPW * NG * 5 / 4 + WG - 1) / WG : 1;              // 16-byte pieces per lane (480 per wave: 8)
-    [[maybe_unused]] uint4 qv[QV];
+    // (two-seat form: both seats' values, each seat's in pieces of its own; the lane's epsilon is its own seat's)
+    constexpr int QSEATS = SEAT ? 1 : 2;                                       // seats whose rows the Q form decodes
+    constexpr int QV = QDEC ? (EPW * NG * 5 / 4 + WG - 1) / WG : 1;              // 16-byte pieces per lane and seat (480 per wave: 8)
+    [[maybe_unused]] uint4 qv[QSEATS][QV];
     [[maybe_unused]] float eps_q = 0.f;
     [[maybe_unused]] uint2 qdraw = make_uint2(0u, 0u);
     if constexpr (QDEC) {
         static_assert(NG * 5 % 4 == 0, "an env's Q values are a whole number of 16-byte pieces");
-        const uint4* qs = reinterpret_cast<const uint4*>(io.q) + (size_t)e0 * (NG * 5 / 4);      // 16-byte aligned (checked by the entry point)
         const int nq = nvalid * (NG * 5 / 4);
+        if constexpr (SEAT) {
+            const uint4* qs = reinterpret_cast<const uint4*>(io.q) + (size_t)e0 * (NG * 5 / 4);      // 16-byte aligned (checked by the entry point)
 #pragma unroll
-        for (int i = 0; i < QV; ++i) {
-            const int v = lane + WG * i;
-            qv[i] = v < nq ? qs[v] : make_uint4(0u, 0u, 0u, 0u);
+            for (int i = 0; i < QV; ++i) {
+                const int v = lane + WG * i;
+                qv[0][i] = v < nq ? qs[v] : make_uint4(0u, 0u, 0u, 0u);
+            }
+            eps_q = io.eps_env ? io.eps_env[e] : io.eps;
+        } else {
+            // [N][2][12][5]: piece v of seat s is piece v % 15 of env v / 15's row s -- 240-byte runs 480 bytes apart
+            const uint4* qs = reinterpret_cast<const uint4*>(io.q) + (size_t)e0 * (2 * NG * 5 / 4);
+#pragma unroll
+            for (int s = 0; s < 2; ++s) {
+#pragma unroll
+                for (int i = 0; i < QV; ++i) {
+                    const int v = lane + WG * i, ev = v / (NG * 5 / 4);
+                    qv[s][i] = v < nq ? qs[(2 * ev + s) * (NG * 5 / 4) + v - ev * (NG * 5 / 4)] : make_uint4(0u, 0u, 0u, 0u);
+                }
+            }
+            eps_q = io.eps_env ? io.eps_env[(size_t)e * 2 + P] : (P ? io.eps1 : io.eps);
         }
-        eps_q = io.eps_env ? io.eps_env[e] : io.eps;
     }
     int turn = (int)(envw & 0xFFu);
     int status = (int)((envw >> 8) & 3u);
@@ -213,9 +232,15 @@ __global__ void __launch_bounds__(WG * WPB) __attribute__((amdgpu_waves_per_eu(2
         if constexpr (QDEC) {
             // the caller's agent call draws two Philox blocks (smart_decode.inc): each lane of the pair draws one -- block P -- and the pair swaps them
             // (DPP), so that both lanes hold the env's coin and draws, no lane idles behind its partner
-            const uint4 b = rng_block(S.seed_lo, S.seed_hi, S.env_id_base + (uint32_t)e, episode, RNG_EXPLORE, (uint32_t)P, turn, 0, io.seat, 0);
-            const uint4 o = make_uint4((uint32_t)xchg1((int)b.x), (uint32_t)xchg1((int)b.y), (uint32_t)xchg1((int)b.z), (uint32_t)xchg1((int)b.w));
-            qdraw = smart_explore_words(P ? o : b, P ? b : o, eps_q);
+            // (two-seat form: each lane is its own seat's agent -- key seat P -- and draws both of its blocks; the seats' calls are independent)
+            if constexpr (SEAT) {
+                const uint4 b = rng_block(S.seed_lo, S.seed_hi, S.env_id_base + (uint32_t)e, episode, RNG_EXPLORE, (uint32_t)P, turn, 0, io.seat, 0);
+                const uint4 o = make_uint4((uint32_t)xchg1((int)b.x), (uint32_t)xchg1((int)b.y), (uint32_t)xchg1((int)b.z), (uint32_t)xchg1((int)b.w));
+                qdraw = smart_explore_words(P ? o : b, P ? b : o, eps_q);
+            } else {
+                qdraw = smart_explore_words(rng_block(S.seed_lo, S.seed_hi, S.env_id_base + (uint32_t)e, episode, RNG_EXPLORE, 0u, turn, 0, P, 0),
+                                            rng_block(S.seed_lo, S.seed_hi, S.env_id_base + (uint32_t)e, episode, RNG_EXPLORE, 1u, turn, 0, P, 0), eps_q);
+            }
         }
     }
     {
@@ -232,13 +257,15 @@ __global__ void __launch_bounds__(WG * WPB) __attribute__((amdgpu_waves_per_eu(2
             if (n <= NN) L.NW[n][E] = (n_in[j >> 1] >> (16 * (j & 1))) & 0xFFFFu;
         }
     }
-    if constexpr (QDEC) {
+    // (Q form: the values of the first seat decoded -- the caller's, or seat 0's -- and the agent calls' draws, held by the lanes of that seat)
+    auto stage_q = [&](int s) {
         uint4* ql = reinterpret_cast<uint4*>(&L.u.sq.q[0][0]);
 #pragma unroll
         for (int i = 0; i < QV; ++i)
-            if (lane + WG * i < EPW * NG * 5 / 4) ql[lane + WG * i] = qv[i];
-        if (P == 0) L.u.sq.draws[E] = qdraw;
-    }
+            if (lane + WG * i < EPW * NG * 5 / 4) ql[lane + WG * i] = qv[s][i];
+        if (P == s) L.u.sq.draws[E] = qdraw;
+    };
+    if constexpr (QDEC) stage_q(0);
     WAVE_SYNC();
     // Every prologue load is waited for here, before the turn loop: a register whose load may still be in flight on SOME path
     // makes the compiler put s_waitcnt vmcnt(0) in front of its first use inside the loop, where it would wait for the previous
@@ -250,54 +277,85 @@ __global__ void __launch_bounds__(WG * WPB) __attribute__((amdgpu_waves_per_eu(2
         // swarm's location is its group word's (the state this launch starts from is what the previous launch's observation shows: with auto_reset a
         // finished env's observation is the first of its next episode), in the caller's own numbering: what obs[45 + 5 s] holds.  Rows of every valid env
         // are decoded and written out, frozen ones included, as evg_smart_get_action writes every env.
+        // (two-seat form: seat 0, then seat 1, each with its own numbering and its own draws)
         const int sw = lane & 15, sub = lane >> 4;
-        const uint64_t own_q = player_node_map(io.seat, L.tab.nib[0]);
-        for (int ps = 0; ps < EPW / 4; ++ps) {
-            const int ep = 4 * ps + sub;                  // env slot of this lane's row
-            const bool act = sw < NG && ep < nvalid;
-            float key = __int_as_float(0x7F800000);      // idle lanes: +inf with ids 12..15, never in front of a swarm
-            int dir = 0, node = 0, loc = 0;
-            if (act) {
-                float v[5];
+        auto decode = [&](int seat) {
+            const uint64_t own_q = player_node_map(seat, L.tab.nib[0]);
+            for (int ps = 0; ps < EPW / 4; ++ps) {
+                const int ep = 4 * ps + sub;              // env slot of this lane's row
+                const bool act = sw < NG && ep < nvalid;
+                float key = __int_as_float(0x7F800000);  // idle lanes: +inf with ids 12..15, never in front of a swarm
+                int dir = 0, node = 0, loc = 0;
+                if (act) {
+                    float v[5];
 #pragma unroll
-                for (int k = 0; k < 5; ++k) v[k] = L.u.sq.q[ep][5 * sw + k];
-                key = smart_best(v, dir);
-                loc = (int)map_node(own_q, L.G[sw][2 * ep + io.seat] & G_LOC_M);
-                node = smart_move(loc, dir);
-            }
-            int rank = smart_rank(key, sw);
-            const uint2 d = L.u.sq.draws[ep];
-            if (ep < nvalid && (d.x >> 31)) {            // get_random_actions
-                rank = smart_explore_rank(d, sw, dir);
-                node = smart_move(loc, dir);
-            }
-            if (act && rank < NA) {
-                L.u.sq.rows[ep][rank] = make_int2(sw, node);
-                L.u.sq.dirs[ep][rank] = make_int2(sw, dir);
-            }
-        }
-        WAVE_SYNC();
-        if (P == io.seat) {
-#pragma unroll
-            for (int i = 0; i < NA; ++i) act_in[i] = L.u.sq.rows[E][i];
-        }
-        if (valid && P == 0 && io.q_explored) io.q_explored[e] = (uint8_t)(qdraw.x >> 31);
-        // rows played and directions: the wave's rows are contiguous in [N][7][2] (e0 * 56 bytes: 16-byte aligned), stored 16 bytes per lane
-        auto put_rows = [&](int32_t* out, const int2* src) {
-            int2* dst = reinterpret_cast<int2*>(out) + (size_t)e0 * NA;
-            if (nvalid == EPW) {
-#pragma unroll
-                for (int i = 0; i < (EPW * NA / 2 + WG - 1) / WG; ++i) {
-                    const int v = lane + WG * i;
-                    if (v < EPW * NA / 2) reinterpret_cast<uint4*>(dst)[v] = reinterpret_cast<const uint4*>(src)[v];
+                    for (int k = 0; k < 5; ++k) v[k] = L.u.sq.q[ep][5 * sw + k];
+                    key = smart_best(v, dir);
+                    loc = (int)map_node(own_q, L.G[sw][2 * ep + seat] & G_LOC_M);
+                    node = smart_move(loc, dir);
                 }
-            } else {
-                for (int v = lane; v < nvalid * NA; v += WG) dst[v] = src[v];      // last, partial workgroup of the grid
+                int rank = smart_rank(key, sw);
+                const uint2 d = L.u.sq.draws[ep];
+                if (ep < nvalid && (d.x >> 31)) {        // get_random_actions
+                    rank = smart_explore_rank(d, sw, dir);
+                    node = smart_move(loc, dir);
+                }
+                if (act && rank < NA) {
+                    L.u.sq.rows[ep][rank] = make_int2(sw, node);
+                    L.u.sq.dirs[ep][rank] = make_int2(sw, dir);
+                }
             }
+            WAVE_SYNC();
         };
-        if (io.q_actions) put_rows(io.q_actions, &L.u.sq.rows[0][0]);
-        if (io.q_directions) put_rows(io.q_directions, &L.u.sq.dirs[0][0]);
-        WAVE_SYNC();                                      // the union is the turn's scratch from here on
+        if constexpr (!SEAT) {
+            // rows [N][2][7][2]: a seat's 56 bytes per env, 112 bytes apart, stored 8 bytes per lane
+            auto put_rows2 = [&](int32_t* out, const int2* src, int s) {
+                int2* dst = reinterpret_cast<int2*>(out) + (size_t)e0 * 2 * NA;
+                for (int v = lane; v < nvalid * NA; v += WG) {
+                    const int ev = v / NA;
+                    dst[(2 * ev + s) * NA + v - ev * NA] = src[v];
+                }
+            };
+#pragma unroll
+            for (int s = 0; s < 2; ++s) {
+                if (s == 1) {
+                    stage_q(1);
+                    WAVE_SYNC();
+                }
+                decode(s);
+                if (P == s) {
+#pragma unroll
+                    for (int i = 0; i < NA; ++i) act_in[i] = L.u.sq.rows[E][i];
+                }
+                if (io.q_actions) put_rows2(io.q_actions, &L.u.sq.rows[0][0], s);
+                if (io.q_directions) put_rows2(io.q_directions, &L.u.sq.dirs[0][0], s);
+                WAVE_SYNC();                              // the next seat's values, then the turn's scratch, replace this seat's rows
+            }
+            if (valid && io.q_explored) io.q_explored[(size_t)e * 2 + P] = (uint8_t)(qdraw.x >> 31);
+        } else {
+            decode(io.seat);
+            if (P == io.seat) {
+#pragma unroll
+                for (int i = 0; i < NA; ++i) act_in[i] = L.u.sq.rows[E][i];
+            }
+            if (valid && P == 0 && io.q_explored) io.q_explored[e] = (uint8_t)(qdraw.x >> 31);
+            // rows played and directions: the wave's rows are contiguous in [N][7][2] (e0 * 56 bytes: 16-byte aligned), stored 16 bytes per lane
+            auto put_rows = [&](int32_t* out, const int2* src) {
+                int2* dst = reinterpret_cast<int2*>(out) + (size_t)e0 * NA;
+                if (nvalid == EPW) {
+#pragma unroll
+                    for (int i = 0; i < (EPW * NA / 2 + WG - 1) / WG; ++i) {
+                        const int v = lane + WG * i;
+                        if (v < EPW * NA / 2) reinterpret_cast<uint4*>(dst)[v] = reinterpret_cast<const uint4*>(src)[v];
+                    }
+                } else {
+                    for (int v = lane; v < nvalid * NA; v += WG) dst[v] = src[v];      // last, partial workgroup of the grid
+                }
+            };
+            if (io.q_actions) put_rows(io.q_actions, &L.u.sq.rows[0][0]);
+            if (io.q_directions) put_rows(io.q_directions, &L.u.sq.dirs[0][0]);
+            WAVE_SYNC();                                  // the union is the turn's scratch from here on
+        }
     }
     const bool observe_only = io.observe_only != 0;
     // stock-entropy mode: the env's MT19937 is advanced by the lane of player 0, in the reference's draw order

@@ -1,7 +1,8 @@
 // step_outputs.inc -- fragment of evg_step_kernel's turn loop (step_kernel.inc): the observation image in LDS, the state store, the coalesced
 // observation write-out and the health rows of envs that start a new episode.
 // reads:  gw[12], cntv[12], st[3], L.NW, L.u.A, turn, status, episode, do_reset, valid / nvalid / e0, iter / nturns
-// writes: L.u.O (the image), io.obs, the state arrays (after the launch's last turn), L.G (next turn's words, persistent form), S.health (restarted envs)
+// writes: L.u.O (the image), io.obs, the state arrays (after the launch's last turn), L.G (next turn's words, persistent form), S.health (restarted envs),
+//         io.feat_shared / io.feat_swarm (one-seat form, two-seat Q form)
     // ---------------- observation of this lane's player (board_state :382-455, player_state :457-501,
     // everglades_env.py:158-171), written as int16 straight into the wave's output image in LDS.
     // Board part by node ID (every LDS read has a constant offset): slot s of player 1's view shows node p1_node_map[s] (:437-439),
@@ -107,18 +108,10 @@
             const bool mine = valid && P == io.seat, partner = valid && P != io.seat;
             // ---- shared [34], by the seat's lane
             if (mine) {
-                uint64_t idle = 0;                                        // nibble n: groups listed at node n (own numbering) that are not in transit (:200-213)
-#pragma unroll
-                for (int k = 0; k < NG; ++k) idle += (uint64_t)(r[48 + 5 * k] == 0 ? 1u : 0u) << (4 * (r[45 + 5 * k] & 15));
-                auto val = [&](int j) -> float {                           // j is a compile-time constant at every call
-                    if (j == 0) return (float)((double)r[0] * (1.0 / 150.0));
-                    if (j < 12) return (float)((double)r[3 + 4 * (j - 1)] * (1.0 / 100.0));
-                    if (j < 23) return (float)((double)r[4 + 4 * (j - 12)] * (1.0 / 100.0));
-                    return (float)((double)(int)((idle >> (4 * (j - 22))) & 15ull) * (1.0 / 12.0));
-                };
+                const uint64_t idle = smart_idle_nibbles(r);             // (the feature values: smart_decode.inc)
                 float2* sp = reinterpret_cast<float2*>(stg + E * 34);
 #pragma unroll
-                for (int j = 0; j < 17; ++j) sp[j] = make_float2(val(2 * j), val(2 * j + 1));
+                for (int j = 0; j < 17; ++j) sp[j] = make_float2(smart_shared_feature(r, 2 * j, idle), smart_shared_feature(r, 2 * j + 1, idle));
             }
             WAVE_SYNC();
             {
@@ -143,7 +136,7 @@
 #pragma unroll
                 for (int k = 0; k < NG; ++k) {
                     loc[k] = r[45 + 5 * k];
-                    hp[k] = (float)((double)((int)r[47 + 5 * k] * (int)r[49 + 5 * k]) * (1.0 / 1000.0));
+                    hp[k] = smart_swarm_health(r, k);
                     mov[k] = (float)r[48 + 5 * k];
                 }
             }
@@ -152,7 +145,7 @@
                 if (partner) {
                     auto val = [&](int j) -> float {                       // j = 13 swarm + feature, compile-time
                         const int sw = j / 13, f = j - 13 * sw;
-                        return f < NN ? (loc[sw] == f + 1 ? 1.f : 0.f) : (f == NN ? hp[sw] : mov[sw]);
+                        return smart_swarm_feature(loc[sw], hp[sw], mov[sw], f);
                     };
                     float4* sp = reinterpret_cast<float4*>(stg + E * 52);
 #pragma unroll
@@ -229,6 +222,62 @@
                     for (int j = 0; j < EP; ++j)
                         if (elem0 + j < limit) out[elem0 + j] = (OT)vals[j];
                 }
+            }
+        }
+    }
+    if constexpr (QDEC && !SEAT) {
+        // ---------------- Smart_State features of BOTH players (evg_step_smart_q, self-play; agents/Smart_State/DQNAgent.py:200-300), compact form: each lane
+        // those of its own observation row, with the values of the one-seat form above (smart_decode.inc).  The two-seat image fills 13 440 B of the union's
+        // 14 336, so nothing can be staged behind it: each lane first copies the 59 values of its row that the features read into registers, and once the
+        // observation write-out above has read the image, the whole union is the staging area -- shared [2][34] of the wave's envs at once (8 704 B), swarm
+        // [2][12][13] in three passes of four swarms (13 312 B) -- stored 16 bytes per lane into outputs that hold the wave's envs contiguously.
+        if (io.feat_shared) {                                                // (wave-uniform)
+            static_assert(sizeof(L.u) >= (size_t)LPW * 52 * 4 && sizeof(L.u) >= (size_t)LPW * 34 * 4, "the two-seat feature staging area");
+            int rv[OBS];                                                     // (only the entries read below stay live)
+            {
+                const int16_t* r = &L.u.O[col * OBS];
+#pragma unroll
+                for (int i = 0; i < OBS; ++i) rv[i] = r[i];
+            }
+            const uint64_t idle = smart_idle_nibbles(rv);
+            WAVE_SYNC();                                                     // the image is dead: the union becomes the staging area
+            float* const stg = reinterpret_cast<float*>(&L.u);
+            const float4* const src = reinterpret_cast<const float4*>(stg);
+            if (valid) {
+                float2* sp = reinterpret_cast<float2*>(stg + col * 34);      // row col = [env][player]: the output's order
+#pragma unroll
+                for (int j = 0; j < 17; ++j) sp[j] = make_float2(smart_shared_feature(rv, 2 * j, idle), smart_shared_feature(rv, 2 * j + 1, idle));
+            }
+            WAVE_SYNC();
+            {
+                float4* dst = reinterpret_cast<float4*>(io.feat_shared + (size_t)e0 * (2 * 34));     // 272 B per env: 16-byte aligned
+                for (int v = lane; v < nvalid * 17; v += WG) dst[v] = src[v];
+            }
+            WAVE_SYNC();
+            float hp[NG], mov[NG];
+#pragma unroll
+            for (int k = 0; k < NG; ++k) {
+                hp[k] = smart_swarm_health(rv, k);
+                mov[k] = (float)rv[48 + 5 * k];
+            }
+#pragma unroll
+            for (int pass = 0; pass < 3; ++pass) {
+                if (valid) {
+                    auto val = [&](int j) -> float {                         // j = 13 swarm + feature, compile-time
+                        const int sw = j / 13, f = j - 13 * sw;
+                        return smart_swarm_feature(rv[45 + 5 * sw], hp[sw], mov[sw], f);
+                    };
+                    float4* sp = reinterpret_cast<float4*>(stg + col * 52);
+#pragma unroll
+                    for (int v = 0; v < 13; ++v) sp[v] = make_float4(val(52 * pass + 4 * v), val(52 * pass + 4 * v + 1), val(52 * pass + 4 * v + 2), val(52 * pass + 4 * v + 3));
+                }
+                WAVE_SYNC();
+                float4* dst = reinterpret_cast<float4*>(io.feat_swarm + (size_t)e0 * (2 * NG * 13)) + 13 * pass;     // 13 float4 per row and pass, rows 39 apart
+                for (int v = lane; v < nvalid * 26; v += WG) {
+                    const int row = v / 13;
+                    dst[row * 39 + (v - 13 * row)] = src[v];
+                }
+                WAVE_SYNC();
             }
         }
     }

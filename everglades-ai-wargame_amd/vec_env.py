@@ -277,6 +277,47 @@ class EvergladesVecEnv(object):
             self._check(rc)
         return obs, self.reward, self.done, self._info
 
+    def step_q(self, q, epsilon, features=None, directions=None, explored=None, actions_out=None, out=None):
+        """The self-play turn from both seats' Q values, in ONE launch (evg_step_smart_q): DQNAgent.get_action for seat 0 and for seat 1 -- each its own
+        epsilon coin, then get_random_actions or get_best_actions, as smart_get_action() -- then step() with both seats' rows.  `q` float32 [N, 2, 12, 5]: row
+        [e, p] is seat p's network output; `epsilon` a float in [0, 1] for both seats, a pair (eps0, eps1), or a float32 tensor [N, 2].  Returns (obs [N, 2, 105],
+        reward [N, 2], done [N], info) like step(); bit-identical to smart_get_action(q[:, p], eps_p, seat=p, obs=<the previous observation>) for both seats,
+        step(rows), then smart_state_compact(p) for both players.  features=(shared [N, 2, 34], swarm [N, 2, 12, 13]), both 16-byte aligned: both players'
+        compact features; `directions` / `actions_out` int32 [N, 2, 7, 2] receive {swarm, direction} / the rows played, `explored` uint8 [N, 2] 1 where a
+        seat's random branch ran.  No host synchronisation and no allocation per call: it can sit inside a captured loop."""
+        torch = _torch()
+        N = self.num_envs
+        self._user(q, (N, 2, _lib.NUM_GROUPS, 5), torch.float32, "q")
+        obs = self.obs if out is None else self._user(out, (N, 2, _lib.OBS_LEN), self.obs_dtype, "out")
+        shared = swarm = None
+        if features is not None:
+            shared, swarm = features
+            self._user(shared, (N, 2, 34), torch.float32, "features[0] (shared)")
+            self._user(swarm, (N, 2, _lib.NUM_GROUPS, 13), torch.float32, "features[1] (swarm)")
+        if directions is not None:
+            self._user(directions, (N, 2, _lib.NUM_ACTIONS, 2), self._int32, "directions")
+        if actions_out is not None:
+            self._user(actions_out, (N, 2, _lib.NUM_ACTIONS, 2), self._int32, "actions_out")
+        if explored is not None:
+            self._user(explored, (N, 2), torch.uint8, "explored")
+        eps_env = None
+        if isinstance(epsilon, torch.Tensor):
+            eps_env = self._user(epsilon, (N, 2), torch.float32, "epsilon")
+            eps0 = eps1 = 0.0
+        elif isinstance(epsilon, (tuple, list)):
+            if len(epsilon) != 2:
+                raise ValueError("epsilon must be a float, a pair (eps0, eps1) or a float32 tensor [N, 2]")
+            eps0, eps1 = epsilon
+        else:
+            eps0 = eps1 = epsilon
+        p = self._p
+        rc = self.L.evg_step_smart_q(self._h, C.c_void_p(q.data_ptr()), float(eps0), float(eps1), self._ptr(eps_env), C.c_void_p(obs.data_ptr()),
+                                     self._ptr(shared), self._ptr(swarm), self._ptr(actions_out), self._ptr(directions), self._ptr(explored),
+                                     p["reward"], p["done"], p["winner"], p["scores"], p["status"], self._stream())
+        if rc:
+            self._check(rc)
+        return obs, self.reward, self.done, self._info
+
     def rollout_vs(self, steps, policy, seat=0, time_kernel=False):
         """`steps` turns of the learner-seat loop driven from native code (evg_rollout_vs_policy): per turn the on-device random_actions
         generator writes the caller seat's rows into a tensor (the stand-in for a policy network's output), then step_vs(policy) runs.

@@ -37,7 +37,8 @@ extern "C" {
 #endif
 
 #define EVG_ABI_VERSION 7
-/* 7: evg_step_vs_policy_smart_q (the Smart_State learner's turn from its Q values: DQNAgent.get_action decoded inside the learner-seat step launch) */
+/* 7: evg_step_vs_policy_smart_q (the Smart_State learner's turn from its Q values: DQNAgent.get_action decoded inside the learner-seat step launch);
+ *    evg_step_smart_q (the self-play turn: both seats' Q values decoded inside one step launch; an added function, no layout changed) */
 /* 6: evg_smart_get_action (DQNAgent.get_action with epsilon > 0), evg_step_vs_policy_smart (the learner-seat turn that also writes the Smart_State
  *    features), evg_get_run_state / evg_set_run_state (agent objects, returns, win counters: checkpoint / resume); reward / score buffers need 8-byte
  *    alignment only (5 asked 16 of every buffer)
@@ -232,6 +233,30 @@ EVG_API int evg_step_vs_policy_smart_q(evg_handle* h, int seat, const float* q, 
                                        void* obs_seat_out, float* shared_out, float* swarm_out,
                                        int32_t* actions_out, int32_t* directions_out, uint8_t* explored_out,
                                        float* reward_out, uint8_t* done_out, int8_t* winner_out, int32_t* scores_out, uint8_t* status_out, void* stream);
+/* The self-play turn in ONE launch, a Smart_State DQNAgent on each seat (agents/Smart_State/training_scripts/dqn_smart_state_self_play.py:120-128,
+ * dqn_smart_state_self_royale.py:135-143): both seats hand their Q values, not their orders.  The launch does DQNAgent.get_action for seat 0 and for seat 1
+ * -- each its own epsilon coin, then get_random_actions or get_best_actions, exactly as evg_smart_get_action -- steps the game with both seats' rows and
+ * writes the next observation and (optionally) the compact features of both players.  The order rows never go through HBM unless asked for.
+ *   q                device float [N][2][12][5] (16-byte aligned): row [e][p] is seat p's network output; domain as in evg_smart_actions (first maximum,
+ *                    a NaN is the maximum and sorts like +inf, stable ascending sort, first seven)
+ *   epsilon0, epsilon1  each seat's epsilon, in [0, 1] (a training seat decays its own, a frozen one plays 0.0)
+ *   epsilon_env      device float [N][2] or NULL: when set, it replaces both scalars
+ *   obs_out, reward_out, done_out, winner_out, scores_out, status_out: as in evg_step (obs_out [N][2][105] in the handle's dtype)
+ *   shared_out, swarm_out  both NULL or both set, both 16-byte aligned: shared [N][2][34], swarm [N][2][12][13], the features of evg_smart_state_compact for
+ *                    player 0 and player 1
+ *   actions_out      device int32 [N][2][7][2] or NULL: the rows both seats played ({swarm, node}: exactly the tensor evg_step takes)
+ *   directions_out   device int32 [N][2][7][2] or NULL: {swarm, direction}
+ *   explored_out     device uint8 [N][2] or NULL: 1 where the seat's random branch ran
+ * Each seat's explore draws keep the key of evg_smart_get_action (env id, episode, turn, seat).  The decode reads each swarm's location (in the seat's own
+ * numbering), the turn and the episode from the state the launch starts from: what the observation of the previous launch shows, also across auto-resets.
+ * Results -- every output above, and the handle's state and run state afterwards -- are bit for bit those of evg_smart_get_action(h, 0, 1, obs_prev[:, 0],
+ * q[:, 0], epsilon0, ...) and evg_smart_get_action(h, 1, 1, obs_prev[:, 1], q[:, 1], epsilon1, ...), then evg_step with both seats' rows, then
+ * evg_smart_state_compact for player 0 and player 1, with obs_prev the observation of the previous launch.  Every env's rows, directions and explored flags are
+ * written, finished ones included.  Keyed-Philox handles only. */
+EVG_API int evg_step_smart_q(evg_handle* h, const float* q, float epsilon0, float epsilon1, const float* epsilon_env,
+                             void* obs_out, float* shared_out, float* swarm_out,
+                             int32_t* actions_out, int32_t* directions_out, uint8_t* explored_out,
+                             float* reward_out, uint8_t* done_out, int8_t* winner_out, int32_t* scores_out, uint8_t* status_out, void* stream);
 /* evg_observe for one seat: obs_seat_out device [N][105] (after evg_reset / evg_set_state, to start a evg_step_vs_policy loop). */
 EVG_API int evg_observe_seat(evg_handle* h, int seat, void* obs_seat_out, void* stream);
 

@@ -1,0 +1,52 @@
+"""CPU tests (no GPU needed) of evg_step_smart_q, the self-play turn from both seats' Q values: the prototype include/evg.h declares and the ctypes binding
+agree, and the kernel instantiation it launches -- the two-seat Q form of the plain single-turn kernel -- fits that kernel's budget (no scratch, no spills,
+the same LDS, 2 waves per SIMD)."""
+import os
+import re
+import subprocess
+
+import pytest
+
+from conftest import ROOT
+
+CSRC = os.path.join(ROOT, "everglades-ai-wargame_amd", "csrc")
+
+
+def _prototype_arity(header, name):
+    m = re.search(r"EVG_API int %s\(([^;]*)\)\s*;" % name, header)
+    assert m, name
+    return len([a for a in m.group(1).split(",") if a.strip()])
+
+
+def test_prototype_and_ctypes_argtypes_have_the_same_arity():
+    import everglades_amd
+    header = open(os.path.join(ROOT, "include", "evg.h")).read()
+    lib = everglades_amd.load_library()
+    assert "evg_step_smart_q" in everglades_amd._lib.EXPORTS
+    assert everglades_amd._lib.ABI_VERSION == 7 and "#define EVG_ABI_VERSION 7" in header
+    assert _prototype_arity(header, "evg_step_smart_q") == len(lib.evg_step_smart_q.argtypes) == 17
+
+
+def test_step_q_is_part_of_the_python_api():
+    import everglades_amd
+    assert callable(getattr(everglades_amd.EvergladesVecEnv, "step_q", None))
+
+
+def _resource_usage():
+    out = subprocess.run(["make", "-s", "-C", CSRC, "resource-usage"], capture_output=True, text=True, check=True)
+    usage = {}
+    for block in re.split(r"remark: Function Name: ", out.stdout + out.stderr)[1:]:
+        name = block.split()[0]
+        usage[name] = dict(re.findall(r"remark:\s+([A-Za-z /\[\]]+?): (\S+) \[", block))
+    return usage
+
+
+@pytest.mark.skipif(not os.path.exists("/opt/rocm/bin/hipcc"), reason="needs hipcc")
+def test_two_seat_q_form_fits_the_plain_kernel_budget():
+    usage = _resource_usage()
+    for ot in "fds":                                             # float, double, int16 observations
+        plain = usage["_ZN3evg15evg_step_kernelI%sLi64ELb0ELb0ELb0ELb0ELi1ELb0EEEvNS_8StepArgsE" % ot]
+        qform = usage["_ZN3evg15evg_step_kernelI%sLi64ELb0ELb0ELb0ELb0ELi1ELb1EEEvNS_8StepArgsE" % ot]
+        assert qform["ScratchSize [bytes/lane]"] == "0" and qform["VGPRs Spill"] == "0" and qform["SGPRs Spill"] == "0", (ot, qform)
+        assert int(qform["LDS Size [bytes/block]"]) <= 20480 and qform["LDS Size [bytes/block]"] == plain["LDS Size [bytes/block]"], (ot, qform)
+        assert qform["Occupancy [waves/SIMD]"] == plain["Occupancy [waves/SIMD]"] == "2", (ot, qform, plain)
