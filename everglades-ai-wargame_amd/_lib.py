@@ -27,7 +27,8 @@ POLICY_NAMES = ["random", "cycle_rush_turn25", "cycle_rush_turn50", "swarm", "al
 POLICY_ALIASES = {"random_actions": 0, "random_actions_2": 0, "swarm_agent": 3, "same_commands_2": 14}
 
 EXPORTS = ["evg_default_tables", "evg_create", "evg_destroy", "evg_reset", "evg_step", "evg_observe", "evg_step_vs_policy", "evg_step_vs_policy_smart",
-           "evg_step_vs_policy_smart_q", "evg_step_smart_q",
+           "evg_step_vs_policy_smart_q", "evg_step_smart_q", "evg_replay_clear", "evg_replay_record", "evg_replay_size", "evg_replay_sample",
+           "evg_replay_gather",
            "evg_observe_seat",
            "evg_random_actions_seat", "evg_smart_state_seat", "evg_smart_state_compact", "evg_check_fault", "evg_rollout_vs_policy", "evg_fog_of_war",
            "evg_sightings", "evg_smart_state", "evg_smart_actions", "evg_smart_get_action", "evg_move_table", "evg_random_actions", "evg_rollout_random", "evg_rollout_policies",
@@ -89,6 +90,21 @@ class EvgConfig(C.Structure):
         ("seed", C.c_uint64), ("env_id_base", C.c_uint64), ("obs_dtype", C.c_int32), ("auto_reset", C.c_int32),
         ("rng_mode", C.c_int32), ("cache_mib", C.c_int32), ("tables", EvgTables),
     ]
+
+
+class EvgReplay(C.Structure):
+    """evg_replay of include/evg.h: the descriptor of a Smart_State replay memory (device pointers the caller owns)."""
+    _fields_ = [
+        ("slots", C.c_int32), ("num_seats", C.c_int32), ("seat", C.c_int32), ("n_step", C.c_int32), ("shaping", C.c_int32),
+        ("shaping_from", C.c_int32), ("shaping_to", C.c_int32), ("transition_episodes", C.c_int32), ("episode_base", C.c_int64),
+        ("shared", C.c_void_p), ("swarm", C.c_void_p), ("directions", C.c_void_p), ("reward", C.c_void_p), ("meta", C.c_void_p),
+        ("count", C.c_void_p), ("env_state", C.c_void_p), ("gamma_pow", C.c_void_p), ("scan", C.c_void_p), ("ctl", C.c_void_p),
+    ]
+
+
+SHAPE_NAMES = ["normalized_score", "basic_reward", "penalize_long_games", "reward_short_games", "transition", "custom"]   # index = EVG_SHAPE_*
+REPLAY_F_NOT_DONE, REPLAY_F_FINAL = 1, 2
+REPLAY_S_EMPTY, REPLAY_S_BAD_HANDLE = 1, 2
 
 
 class EvgError(RuntimeError):
@@ -163,6 +179,12 @@ def load(path=None):
     L.evg_step_vs_policy_smart_q.argtypes = [vp, C.c_int, vp, C.c_float, vp, C.c_int, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]
     L.evg_step_smart_q.argtypes = [vp, vp, C.c_float, C.c_float, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]
     L.evg_observe_seat.argtypes = [vp, C.c_int, vp, vp]
+    rp = C.POINTER(EvgReplay)
+    L.evg_replay_clear.argtypes = [vp, rp, vp]
+    L.evg_replay_record.argtypes = [vp, rp, C.c_int64, vp, vp, vp, vp]
+    L.evg_replay_size.argtypes = [vp, rp, vp]
+    L.evg_replay_sample.argtypes = [vp, rp, C.c_int, C.c_uint64, vp, vp, vp, vp, vp, vp, vp]
+    L.evg_replay_gather.argtypes = [vp, rp, C.c_int, vp, vp, vp, vp, vp, vp, vp]
     L.evg_random_actions_seat.argtypes = [vp, C.c_int, vp, vp]
     L.evg_smart_state_seat.argtypes = [vp, vp, vp, vp]
     L.evg_smart_state_compact.argtypes = [vp, C.c_int, vp, vp, vp, vp]

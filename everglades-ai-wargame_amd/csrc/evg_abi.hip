@@ -840,6 +840,93 @@ int evg_smart_get_action(evg_handle* h, int seat, int obs_one_seat, const void* 
     return EVG_OK;
 } catch (...) { return on_exception(); }
 
+// ---- the Smart_State replay memory (include/evg.h, evg_replay_*) ----
+static int check_replay(const evg_handle* h, const evg_replay* m) {
+    if (!h || !m) return fail(EVG_ERR_INVALID, "null handle or replay descriptor");
+    if (m->num_seats != 1 && m->num_seats != 2) return fail(EVG_ERR_INVALID, "replay: num_seats must be 1 or 2 (got %d)", m->num_seats);
+    if (m->num_seats == 1 && (m->seat < 0 || m->seat > 1)) return fail(EVG_ERR_INVALID, "replay: seat must be 0 or 1 (got %d)", m->seat);
+    if (m->n_step < 1 || m->n_step > 64) return fail(EVG_ERR_INVALID, "replay: n_step must lie in 1..64 (got %d)", m->n_step);
+    if (m->slots < m->n_step + 2)
+        return fail(EVG_ERR_INVALID, "replay: slots %d < n_step + 2 = %d (the ring keeps slots - 1 turns, and a record needs its next one n turns later)",
+                    m->slots, m->n_step + 2);
+    if ((long long)m->slots * h->S.N * m->num_seats > 0x7FFFFFFFLL / 8) return fail(EVG_ERR_INVALID, "replay: slots x N x S too large");
+    if (m->shaping < EVG_SHAPE_NORMALIZED_SCORE || m->shaping > EVG_SHAPE_CUSTOM) return fail(EVG_ERR_INVALID, "replay: unknown shaping %d", m->shaping);
+    if (m->shaping == EVG_SHAPE_TRANSITION) {
+        if (m->shaping_from < EVG_SHAPE_NORMALIZED_SCORE || m->shaping_from > EVG_SHAPE_REWARD_SHORT_GAMES || m->shaping_to < EVG_SHAPE_NORMALIZED_SCORE ||
+            m->shaping_to > EVG_SHAPE_REWARD_SHORT_GAMES)
+            return fail(EVG_ERR_INVALID, "replay: transition shaping needs two base functions (got %d, %d)", m->shaping_from, m->shaping_to);
+        if (m->transition_episodes < 1) return fail(EVG_ERR_INVALID, "replay: transition_episodes must be >= 1");
+    }
+    if (!m->shared || !m->swarm || !m->directions || !m->reward || !m->meta || !m->count || !m->env_state || !m->gamma_pow || !m->scan || !m->ctl)
+        return fail(EVG_ERR_INVALID, "replay: every buffer of the descriptor is required");
+    EVG_NEED_ALIGNED16(m->shared); EVG_NEED_ALIGNED16(m->swarm); EVG_NEED_ALIGNED16(m->directions); EVG_NEED_ALIGNED16(m->reward);
+    EVG_NEED_ALIGNED16(m->meta); EVG_NEED_ALIGNED16(m->count); EVG_NEED_ALIGNED16(m->env_state); EVG_NEED_ALIGNED16(m->gamma_pow);
+    EVG_NEED_ALIGNED16(m->scan); EVG_NEED_ALIGNED16(m->ctl);
+    return EVG_OK;
+}
+
+int evg_replay_clear(evg_handle* h, const evg_replay* m, void* stream) try {
+    { const int rc = check_replay(h, m); if (rc) return rc; }
+    EVG_ON_DEVICE(h);
+    const int rc = launch_replay_clear(h->S, *m, stream);
+    if (rc) return fail(EVG_ERR_HIP, "replay clear launch failed: %s", hipGetErrorString((hipError_t)rc));
+    return EVG_OK;
+} catch (...) { return on_exception(); }
+
+int evg_replay_record(evg_handle* h, const evg_replay* m, int64_t turn, const float* reward_in, const uint8_t* done_in, const float* custom_in,
+                      void* stream) try {
+    { const int rc = check_replay(h, m); if (rc) return rc; }
+    if (turn < 0) return fail(EVG_ERR_INVALID, "replay_record: turn must be >= 0");
+    if (!done_in || (m->shaping == EVG_SHAPE_CUSTOM ? !custom_in : !reward_in))
+        return fail(EVG_ERR_INVALID, "replay_record: done_in and %s are required", m->shaping == EVG_SHAPE_CUSTOM ? "custom_in" : "reward_in");
+    EVG_NEED_ALIGNED8(reward_in);
+    EVG_ON_DEVICE(h);
+    const int rc = launch_replay_record(h->S, *m, (long long)turn, reward_in, done_in, custom_in, stream);
+    if (rc) return fail(EVG_ERR_HIP, "replay record launch failed: %s", hipGetErrorString((hipError_t)rc));
+    return EVG_OK;
+} catch (...) { return on_exception(); }
+
+int evg_replay_size(evg_handle* h, const evg_replay* m, void* stream) try {
+    { const int rc = check_replay(h, m); if (rc) return rc; }
+    EVG_ON_DEVICE(h);
+    const int rc = launch_replay_count(h->S, *m, 0, stream);
+    if (rc) return fail(EVG_ERR_HIP, "replay count launch failed: %s", hipGetErrorString((hipError_t)rc));
+    return EVG_OK;
+} catch (...) { return on_exception(); }
+
+static int check_batch_out(int batch, const float* swarm_obs, const int64_t* action, const float* next_state, const float* reward, const uint8_t* not_done,
+                           const int32_t* handles) {
+    if (batch < 1) return fail(EVG_ERR_INVALID, "replay: batch must be >= 1 (got %d)", batch);
+    if (batch > (1 << 24)) return fail(EVG_ERR_INVALID, "replay: batch %d > 2^24", batch);
+    if (!swarm_obs || !action || !next_state || !reward || !not_done || !handles)
+        return fail(EVG_ERR_INVALID, "replay: swarm_obs, action, next_state, reward, not_done and handles are required");
+    EVG_NEED_ALIGNED16(swarm_obs); EVG_NEED_ALIGNED16(action); EVG_NEED_ALIGNED16(next_state); EVG_NEED_ALIGNED16(reward);
+    EVG_NEED_ALIGNED16(not_done); EVG_NEED_ALIGNED16(handles);
+    return EVG_OK;
+}
+
+int evg_replay_sample(evg_handle* h, const evg_replay* m, int batch, uint64_t seed, float* swarm_obs, int64_t* action, float* next_state, float* reward,
+                      uint8_t* not_done, int32_t* handles, void* stream) try {
+    { const int rc = check_replay(h, m); if (rc) return rc; }
+    { const int rc = check_batch_out(batch, swarm_obs, action, next_state, reward, not_done, handles); if (rc) return rc; }
+    EVG_ON_DEVICE(h);
+    int rc = launch_replay_count(h->S, *m, 1, stream);
+    if (!rc) rc = launch_replay_draw(h->S, *m, batch, seed, handles, stream);
+    if (!rc) rc = launch_replay_gather(h->S, *m, batch, handles, swarm_obs, action, next_state, reward, not_done, stream);
+    if (rc) return fail(EVG_ERR_HIP, "replay sample launch failed: %s", hipGetErrorString((hipError_t)rc));
+    return EVG_OK;
+} catch (...) { return on_exception(); }
+
+int evg_replay_gather(evg_handle* h, const evg_replay* m, int batch, const int32_t* handles, float* swarm_obs, int64_t* action, float* next_state,
+                      float* reward, uint8_t* not_done, void* stream) try {
+    { const int rc = check_replay(h, m); if (rc) return rc; }
+    { const int rc = check_batch_out(batch, swarm_obs, action, next_state, reward, not_done, handles); if (rc) return rc; }
+    EVG_ON_DEVICE(h);
+    const int rc = launch_replay_gather(h->S, *m, batch, handles, swarm_obs, action, next_state, reward, not_done, stream);
+    if (rc) return fail(EVG_ERR_HIP, "replay gather launch failed: %s", hipGetErrorString((hipError_t)rc));
+    return EVG_OK;
+} catch (...) { return on_exception(); }
+
 void evg_move_table(int32_t* table /* [11][5] */) {
     // agents/Smart_State/Move_Translation.py:3-97: node reached from (0-indexed) node n0 in direction 0 left, 1 right, 2 up, 3 down, 4 stay
     static const int32_t T[5][11] = {{1, 1, 3, 1, 2, 3, 4, 5, 6, 7, 11}, {1, 5, 6, 7, 8, 9, 10, 11, 9, 11, 11}, {2, 2, 2, 3, 5, 6, 7, 8, 8, 9, 8},

@@ -213,5 +213,12 @@ int launch_smart_actions(const DevState& S, int player, const void* obs, int sea
                          int32_t* directions,
                          int obs_dtype, void* stream, const SmartExplore* explore = nullptr /* NULL: get_best_actions only */);
 int launch_pack_results(const DevState& S, float* out, long long* counts /* device [4] or NULL */, void* stream);
+// the Smart_State replay memory (replay_kernels.inc); `m` is validated by the caller (evg_abi.hip)
+int launch_replay_clear(const DevState& S, const evg_replay& m, void* stream);
+int launch_replay_record(const DevState& S, const evg_replay& m, long long turn, const float* reward, const uint8_t* done, const float* custom, void* stream);
+int launch_replay_count(const DevState& S, const evg_replay& m, int count_call /* 1: a sample's count (advances the call counter) */, void* stream);
+int launch_replay_draw(const DevState& S, const evg_replay& m, int batch, uint64_t seed, int32_t* handles, void* stream);
+int launch_replay_gather(const DevState& S, const evg_replay& m, int batch, const int32_t* handles, float* swarm_obs, int64_t* action, float* next_state,
+                         float* reward, uint8_t* not_done, void* stream);
 
 }  // namespace evg

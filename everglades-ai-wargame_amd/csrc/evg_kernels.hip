@@ -73,6 +73,7 @@ namespace evg {
 #undef io
 
 #include "side_kernels.inc"     // pack, chunk-queue check, reset, seeding, action generators, fog planes, Smart_State features
+#include "replay_kernels.inc"   // the Smart_State learner's n-step replay memory: record, count, draw, gather
 
 // ---------------------------------------------------------------------------------------------
 // launchers

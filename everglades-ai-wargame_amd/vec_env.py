@@ -468,6 +468,13 @@ class EvergladesVecEnv(object):
             self._check(rc)
         return out
 
+    def smart_replay(self, capacity_turns, n_step=1, gamma=0.999, shaping="normalized_score", seats=0, episode_base=0):
+        """The Smart_State learner's n-step replay memory on the device for this env (everglades_amd.SmartReplay: Multi_Step.NStepModule +
+        DQNAgent.remember_game_state / end_of_episode / optimize_model's batch).  Storage is allocated once; record / sample / gather run without a host
+        synchronisation.  seats: 0 or 1 for a step_vs_q loop, (0, 1) for step_q."""
+        from .replay import SmartReplay
+        return SmartReplay(self, capacity_turns, n_step=n_step, gamma=gamma, shaping=shaping, seats=seats, episode_base=episode_base)
+
     @staticmethod
     def expand_smart_state(shared, swarm):
         """[N, 12, 59] from the compact pair (for checks; a consumer would rather split its first layer's weights)."""

@@ -1,0 +1,89 @@
+#!/usr/bin/env python3
+"""The Smart_State learner's training loop (agents/Smart_State/training_scripts/dqn_smart_state_training.py:90-140) end to end on the device: N envs
+against a scripted bot, one step launch per turn from the network's Q values (step_vs_q), the replay memory filled on the device (SmartReplay.record:
+reward_shaping.reward_short_games + remember_game_state + end_of_episode's n-step push) and optimize_model fed by SmartReplay.sample.
+
+    features --QNetwork--> Q --evg_step_vs_policy_smart_q--> reward, done, next features (written into the memory's next slot)
+             --evg_replay_record--> shaped reward, n-step sums --evg_replay_sample--> swarm_obs, action, next_state_swarms, reward, not_done
+             --optimize_model (DQNAgent.py:336-385, torch)--> loss
+
+The network is the reference's QNetwork shape (59-60-60-5, relu) with random weights; the loss is F.smooth_l1_loss of the reference, the target the mean
+over swarms of the best target-network Q of the next state, times gamma ** n_step, plus the n-step reward.  A DQN loss need not decrease.
+
+    python examples/smart_state_training.py [envs] [turns] [batch]
+"""
+import os
+import sys
+import time
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+import torch
+import torch.nn.functional as F
+import everglades_amd as evg
+
+GAMMA, N_STEP, LR = 0.999, 1, 1e-4
+
+
+def make_qnet(device, seed=0):
+    torch.manual_seed(seed)
+    return torch.nn.Sequential(torch.nn.Linear(59, 60), torch.nn.ReLU(), torch.nn.Linear(60, 60), torch.nn.ReLU(), torch.nn.Linear(60, 5)).to(device)
+
+
+def q_values(net, shared, swarm):
+    """Q [N, 12, 5] from the compact features: features[e, s] = cat(shared[e], swarm[e, s], onehot(s))."""
+    return net(evg.EvergladesVecEnv.expand_smart_state(shared, swarm)).contiguous()
+
+
+def optimize_model(policy, target, opt, batch):
+    """DQNAgent.optimize_model (DQNAgent.py:336-385) on the sampled operands."""
+    swarm_obs, action, next_state, reward, not_done = batch
+    predicted = policy(swarm_obs).gather(1, action.unsqueeze(1))
+    with torch.no_grad():
+        nxt = target(next_state)                                       # [B, 12, 5]; zeros rows where not_done is False give Q of zeros: mask below
+        nxt = torch.where(not_done[:, None, None], nxt, torch.zeros_like(nxt))
+        future = nxt.amax(2).mean(1)
+        estimated = future * (GAMMA ** N_STEP) + reward
+    loss = F.smooth_l1_loss(predicted, estimated.unsqueeze(1))
+    opt.zero_grad()
+    loss.backward()
+    for p in policy.parameters():
+        p.grad.data.clamp_(-1, 1)
+    opt.step()
+    return loss.detach()
+
+
+def main(num_envs=8192, turns=300, batch=1024, opponent="swarm_agent", seat=0, seed=1, epsilon=0.3):
+    env = evg.EvergladesVecEnv(num_envs, seed=seed, auto_reset=True)
+    dev = env.device
+    policy, target = make_qnet(dev, 0), make_qnet(dev, 0)
+    target.load_state_dict(policy.state_dict())
+    opt = torch.optim.Adam(policy.parameters(), lr=LR)
+    mem = env.smart_replay(8, n_step=N_STEP, gamma=GAMMA, shaping="reward_short_games", seats=seat)
+    env.reset()
+    env.smart_state_compact(-1, env.observe_seat(seat), *mem.slot_features(0))   # record 0's features
+    losses = []
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    for t in range(turns):
+        with torch.no_grad():
+            q = q_values(policy, *mem.slot_features(t))
+        env.step_vs_q(opponent, q, epsilon, seat=seat, features=mem.slot_features(t + 1), directions=mem.slot_directions(t))
+        mem.record()
+        if t >= N_STEP + 1:
+            losses.append(optimize_model(policy, target, opt, mem.sample(batch, seed=seed)))
+        if t % 100 == 99:
+            target.load_state_dict(policy.state_dict())
+    torch.cuda.synchronize()
+    dt = time.perf_counter() - t0
+    losses = torch.stack(losses).cpu()
+    mem.check()
+    print("%d envs x %d turns in %.3f s (%.1f M env-steps/s, network and learning included); memory holds %d transitions; loss first %.4g last %.4g, "
+          "all finite: %s" % (num_envs, turns, dt, num_envs * turns / dt / 1e6, int(mem.size().item()), float(losses[0]), float(losses[-1]),
+                               bool(torch.isfinite(losses).all())))
+    env.close()
+    return losses
+
+
+if __name__ == "__main__":
+    a = sys.argv[1:]
+    main(int(a[0]) if a else 8192, int(a[1]) if len(a) > 1 else 300, int(a[2]) if len(a) > 2 else 1024)

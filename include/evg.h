@@ -514,6 +514,104 @@ EVG_API int evg_state_bytes_per_env(const evg_handle* h);
 EVG_API const char* evg_last_error(void);
 EVG_API int evg_abi_version(void);
 
+/* ---------------------------------------------------------------------------------------------------------------------------------------------------
+ * The Smart_State learner's n-step replay memory on the device (agents/Smart_State/Multi_Step.py NStepModule + NStepReplayMemory, DQNAgent.py:312-385
+ * remember_game_state / end_of_episode / optimize_model's batch).  Added under ABI 7: new functions and one new descriptor struct; nothing that existed
+ * changed.
+ *
+ * Storage is caller-owned device memory described by an evg_replay descriptor, allocated once (everglades_amd.SmartReplay does it).  It is a ring of `slots` TURNS,
+ * not of transitions: slot t % slots holds record t, the turn-t state of every (env, seat) -- N envs x S seats, S = 1 for evg_step_vs_policy_smart_q,
+ * S = 2 for evg_step_smart_q.  A record is the compact features of the observation the agent acted on (the `features` views a step writes for the NEXT
+ * turn: pass slot t + 1 to step t), the {swarm, direction} rows step t wrote (`directions` view of slot t) and the metadata evg_replay_record writes.
+ * While record t is the newest one, slot (t + 1) % slots already holds the features of record t + 1, so the ring keeps slots - 1 turns: records
+ * t - slots + 2 .. t.  A record is sampled only once it is FINALISED (its n-step sum is known) and only while both it and its next record (n turns later,
+ * same episode) are kept: slots >= n_step + 2.  One turn of 65 536 envs already holds more transitions than the reference's MEMORY_SIZE (100 000).
+ *
+ * Layout (record r = (slot * N + env) * S + seat; every buffer 16-byte aligned):
+ *   shared      float [slots] x EVG_REPLAY_SHARED_STRIDE(N, S)   slot k = shared [N][S][34] at shared + k * stride (padded to 16 bytes)
+ *   swarm       float [slots][N][S][12][13]
+ *   directions  int32 [slots] x EVG_REPLAY_DIRS_STRIDE(N, S)     slot k = [N][S][7][2] {swarm, direction}
+ *   reward      double [slots][N][S][2]   {shaped reward of the turn, n-step summed reward (valid once finalised)}
+ *   meta        int32 [slots][N][S][4]    {turn number in the episode, episode index on the handle, flags EVG_REPLAY_F_*, 0}
+ *   count       uint8 [slots][N][S]       transitions of the record: 0 until finalised
+ *   env_state   int32 [N][4]              per env: turn, episode, records of the episode kept, frozen (set by evg_replay_clear, advanced by record)
+ *   gamma_pow   double [n_step]           gamma ** k for k < n_step, computed on the HOST (Python's float power; a device pow may differ in the last bit)
+ *   scan        int32 [EVG_REPLAY_SCAN_INTS(slots, N, S)]  work space of evg_replay_sample / evg_replay_size
+ *   ctl         uint64 [4]                {sample calls so far, status bits EVG_REPLAY_S_*, transitions counted by the last scan, call index in use}
+ * ------------------------------------------------------------------------------------------------------------------------------------------------- */
+#define EVG_REPLAY_SHARED_STRIDE(N, S) (((int64_t)(N) * (S) * 34 + 3) / 4 * 4)
+#define EVG_REPLAY_DIRS_STRIDE(N, S) (((int64_t)(N) * (S) * 14 + 3) / 4 * 4)
+#define EVG_REPLAY_SCAN_INTS(slots, N, S) (((int64_t)(slots) * (N) * (S) + 3) / 4 + ((int64_t)(slots) * (N) * (S) + 1023) / 1024)
+enum { EVG_REPLAY_F_NOT_DONE = 1, EVG_REPLAY_F_FINAL = 2 };
+/* status bits of ctl[1] (sticky until evg_replay_clear): a sample from an empty memory wrote zeros; a gather got a handle that names no transition */
+enum { EVG_REPLAY_S_EMPTY = 1, EVG_REPLAY_S_BAD_HANDLE = 2 };
+/* reward shaping of utils/reward_shaping.py(player, rewardArray, done, turnNum), evaluated in float64 in the reference's order of operations */
+enum {
+    EVG_SHAPE_NORMALIZED_SCORE = 0,     /* rewardArray[player]                                                    */
+    EVG_SHAPE_BASIC_REWARD = 1,         /* done and won: 1.0, else 0.0                                            */
+    EVG_SHAPE_PENALIZE_LONG_GAMES = 2,  /* done: won 100.0, else -0.1; not done: -0.001                           */
+    EVG_SHAPE_REWARD_SHORT_GAMES = 3,   /* done: won (150.0 - turnNum) / 150.0, else -1.0; not done: 0.0          */
+    EVG_SHAPE_TRANSITION = 4,           /* transition(from, to, K, i_episode): ratio = min(1.0, i_episode / K), from * (1.0 - ratio) + to * ratio */
+    EVG_SHAPE_CUSTOM = 5                /* the caller's float32 [N][S] of evg_replay_record                       */
+};
+
+typedef struct evg_replay {
+    int32_t slots;                 /* >= n_step + 2 (the ring keeps slots - 1 turns)                                        */
+    int32_t num_seats;             /* S: 1 or 2                                                                             */
+    int32_t seat;                  /* S == 1: the learner's seat, 0 or 1 (the reward's player); ignored for S == 2          */
+    int32_t n_step;                /* >= 1 (N_STEP of DQNAgent.py)                                                          */
+    int32_t shaping;               /* EVG_SHAPE_*                                                                           */
+    int32_t shaping_from, shaping_to;   /* EVG_SHAPE_TRANSITION: the two functions (EVG_SHAPE_NORMALIZED_SCORE .. _REWARD_SHORT_GAMES) */
+    int32_t transition_episodes;   /* EVG_SHAPE_TRANSITION: fully_transitioned_episode_num K >= 1                           */
+    int64_t episode_base;          /* i_episode = episode_base + 1 + the env's episode index on the handle                  */
+    float* shared;
+    float* swarm;
+    int32_t* directions;
+    double* reward;
+    int32_t* meta;
+    uint8_t* count;
+    int32_t* env_state;
+    const double* gamma_pow;
+    int32_t* scan;
+    unsigned long long* ctl;
+} evg_replay;
+
+/* Empties the memory (count, meta, reward, status) and sets every env's counters from the handle's state as it will be when the stream reaches the
+ * call: turn = current turn, episode = the handle's episode index, frozen = finished without auto_reset.  Call it after evg_reset / evg_set_state.
+ * Enqueued on `stream`; no synchronisation. */
+EVG_API int evg_replay_clear(evg_handle* h, const evg_replay* m, void* stream);
+/* One launch after step `turn` (0, 1, 2, ... since the last clear; the caller's counter, so that a loop can be captured): writes record `turn`'s
+ * metadata and finalises what the n-step rule allows (Multi_Step.py getSummedReward / addGameToReplayMemory):
+ *   - the turn's shaped reward, from reward_in [N][2] (player = seat) and done_in [N] of the step, or from custom_in float [N][S] (EVG_SHAPE_CUSTOM);
+ *   - record turn - n of the same episode: summed = r[s] + sum_{k<n} gamma_pow[k] * r[s+k+1] (the first future term is not discounted, as in the
+ *     reference), not_done = 1 (its next record, turn, exists);
+ *   - if the step ended the episode, records turn - n + 1 .. turn of it get their truncated sums and not_done = 0; the env's counters then start the
+ *     next episode (turn 0, episode + 1) or, without auto_reset, freeze it: a frozen env records nothing;
+ *   - a finalised record holds one transition per order row whose swarm is in 0..11, is not named by an earlier row, and whose direction is not 0
+ *     (node_moved_to = direction - 1 and -1 means "no action"); the transition's action is direction - 1;
+ *   - slot (turn + 1) % slots is emptied: the step has just overwritten its features with record turn + 1's.
+ * reward_in / done_in / custom_in: device; reward_in 8-byte aligned. */
+EVG_API int evg_replay_record(evg_handle* h, const evg_replay* m, int64_t turn, const float* reward_in, const uint8_t* done_in, const float* custom_in,
+                              void* stream);
+/* The number of transitions of the memory, counted on the device (a scan over the per-record counts) into ctl[2]; no host read-back. */
+EVG_API int evg_replay_size(evg_handle* h, const evg_replay* m, void* stream);
+/* optimize_model's batch (DQNAgent.py:336-385; three launches: count, draw, gather) for `batch` transitions drawn uniformly WITH replacement over the transitions of the memory (the
+ * reference's random.sample draws without replacement): draw i is Philox(seed, call index, i), the call index being ctl[0] (incremented by the call,
+ * on the device).  Outputs, row i (all 16-byte aligned):
+ *   swarm_obs   float [batch][59]      shared(34) ++ swarm[s](13) ++ onehot(s)  (create_swarm_obs of the acted-on observation)
+ *   action      int64 [batch]          direction - 1
+ *   next_state  float [batch][12][59]  the 12 swarm rows of the record n turns later; zeros where not_done = 0
+ *   reward      float [batch]          the float64 n-step sum rounded once
+ *   not_done    uint8 [batch]          doesNotHitDone
+ *   handles     int32 [batch][4]: {slot, env, seat, order row} of the drawn transitions (all -1 when the memory is empty); the gather reads them
+ * An empty memory cannot be refused on the host (its size lives on the device): the outputs are then zeros and ctl[1] gets EVG_REPLAY_S_EMPTY. */
+EVG_API int evg_replay_sample(evg_handle* h, const evg_replay* m, int batch, uint64_t seed, float* swarm_obs, int64_t* action, float* next_state,
+                              float* reward, uint8_t* not_done, int32_t* handles, void* stream);
+/* The same outputs for caller-chosen handles int32 [batch][4] (deterministic).  A handle that names no transition of the memory gets zeros and sets
+ * EVG_REPLAY_S_BAD_HANDLE in ctl[1]. */
+EVG_API int evg_replay_gather(evg_handle* h, const evg_replay* m, int batch, const int32_t* handles, float* swarm_obs, int64_t* action, float* next_state,
+                              float* reward, uint8_t* not_done, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

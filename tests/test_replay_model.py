@@ -1,0 +1,96 @@
+"""CPU tests (no GPU needed) of the Smart_State replay memory: the host model (tests/replay_model.py) against the reference's own n-step memory
+(tests/golden/smart_replay.npz, tools/gen_replay_golden.py), the ctypes binding against include/evg.h, and the new kernels' resource budget."""
+import os
+import re
+import subprocess
+
+import numpy as np
+import pytest
+
+from conftest import ROOT, load_golden
+from replay_model import ReplayModel, SHAPES
+
+CSRC = os.path.join(ROOT, "everglades-ai-wargame_amd", "csrc")
+
+
+def variant_shaping(params):
+    n, gamma, code, f1, f2, K, base = params
+    shaping = ("transition", SHAPES[int(f1)], SHAPES[int(f2)], int(K)) if int(code) == 4 else SHAPES[int(code)]
+    return int(n), float(gamma), shaping, int(base)
+
+
+def play_model(d, v):
+    n, gamma, shaping, base = variant_shaping(d[v + "_params"])
+    T = len(d[v + "_done"])
+    m = ReplayModel(1, 1, T + 1, n, gamma, shaping, episode_base=base)          # no wrap: slot = record
+    for t in range(T):
+        m.record(d[v + "_dirs"][t][None], d[v + "_reward"][t][None].astype(np.float32), d[v + "_done"][t][None])
+    return m
+
+
+@pytest.mark.parametrize("v", ["a", "b", "c"])
+def test_host_model_equals_the_reference_memory(v):
+    d = load_golden("smart_replay.npz")
+    m = play_model(d, v)
+    got = m.transitions()
+    want, want_r = d[v + "_tr"], d[v + "_tr_reward"]
+    key = lambda rec, sw: rec * 16 + sw
+    order = np.argsort(key(got["slot"], got["swarm"]))
+    worder = np.argsort(key(want[:, 0], want[:, 1]))
+    assert len(order) == len(worder) == m.size()
+    assert np.array_equal(got["slot"][order], want[worder, 0]) and np.array_equal(got["swarm"][order], want[worder, 1])
+    assert np.array_equal(got["action"][order], want[worder, 2])
+    assert np.array_equal(got["next_slot"][order], want[worder, 3])
+    assert np.array_equal(got["not_done"][order].astype(np.int32), want[worder, 4])
+    # the env reward reaches the device as float32: 1e-6 relative
+    assert np.allclose(got["reward"][order], want_r[worder], rtol=1e-6, atol=1e-12)
+    # per-turn metadata: turn and episode of every record
+    assert np.array_equal(m.meta[:len(d[v + "_turn"]), 0, 0, 0], d[v + "_turn"])
+    assert np.array_equal(m.meta[:len(d[v + "_turn"]), 0, 0, 1], d[v + "_episode"])
+
+
+def test_fixture_covers_both_sides_of_the_transition_and_a_short_episode():
+    d = load_golden("smart_replay.npz")
+    assert int(d["a_params"][6]) + 1 < int(d["a_params"][5]) < int(d["a_params"][6]) + int(d["a_done"].sum())     # i_episode on both sides of K
+    ends = np.flatnonzero(d["c_done"])
+    assert ends[0] + 1 < int(d["c_params"][0])                                   # an episode shorter than n
+    assert (d["a_dirs"][:, :, 1] == 0).any()                                     # rows with direction 0 push nothing
+
+
+def _prototype_arity(header, name):
+    m = re.search(r"EVG_API int %s\(([^;]*)\)\s*;" % name, header)
+    assert m, name
+    return len([a for a in m.group(1).split(",") if a.strip()])
+
+
+def test_prototypes_exports_and_ctypes_agree():
+    import ctypes
+    import everglades_amd
+    header = open(os.path.join(ROOT, "include", "evg.h")).read()
+    lib = everglades_amd.load_library()
+    want = {"evg_replay_clear": 3, "evg_replay_record": 7, "evg_replay_size": 3, "evg_replay_sample": 11, "evg_replay_gather": 10}
+    for name, k in want.items():
+        assert name in everglades_amd._lib.EXPORTS
+        assert _prototype_arity(header, name) == len(getattr(lib, name).argtypes) == k, name
+    # the descriptor: field order and size of evg_replay (8 int32, one int64, 10 pointers)
+    body = re.search(r"typedef struct evg_replay \{(.*?)\} evg_replay;", header, re.S).group(1)
+    names = re.findall(r"\b(\w+)\s*(?:,\s*(\w+))?\s*;", re.sub(r"/\*.*?\*/", "", body, flags=re.S))
+    fields = [x for pair in names for x in pair if x]
+    assert fields == [f for f, _ in everglades_amd._lib.EvgReplay._fields_]
+    assert ctypes.sizeof(everglades_amd._lib.EvgReplay) == 8 * 4 + 8 + 10 * 8
+    assert callable(getattr(everglades_amd.EvergladesVecEnv, "smart_replay", None)) and everglades_amd.SmartReplay
+
+
+@pytest.mark.skipif(not os.path.exists("/opt/rocm/bin/hipcc"), reason="needs hipcc")
+def test_replay_kernels_fit_their_budget():
+    out = subprocess.run(["make", "-s", "-C", CSRC, "resource-usage"], capture_output=True, text=True, check=True)
+    usage = {}
+    for block in re.split(r"remark: Function Name: ", out.stdout + out.stderr)[1:]:
+        usage[block.split()[0]] = dict(re.findall(r"remark:\s+([A-Za-z /\[\]]+?): (\S+) \[", block))
+    names = [k for k in usage if "evg_replay_" in k]
+    assert len(names) == 6, names
+    for k in names:
+        u = usage[k]
+        assert u["ScratchSize [bytes/lane]"] == "0" and u["VGPRs Spill"] == "0" and u["SGPRs Spill"] == "0", (k, u)
+        assert int(u["VGPRs"]) <= 64 and int(u["Occupancy [waves/SIMD]"]) >= 8, (k, u)
+        assert int(u["LDS Size [bytes/block]"]) <= 16384, (k, u)
