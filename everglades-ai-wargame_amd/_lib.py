@@ -28,7 +28,7 @@ POLICY_ALIASES = {"random_actions": 0, "random_actions_2": 0, "swarm_agent": 3, 
 
 EXPORTS = ["evg_default_tables", "evg_create", "evg_destroy", "evg_reset", "evg_step", "evg_observe", "evg_step_vs_policy", "evg_step_vs_policy_smart",
            "evg_step_vs_policy_smart_q", "evg_step_smart_q", "evg_replay_clear", "evg_replay_record", "evg_replay_size", "evg_replay_sample",
-           "evg_replay_gather",
+           "evg_replay_gather", "evg_smart_qnet",
            "evg_observe_seat",
            "evg_random_actions_seat", "evg_smart_state_seat", "evg_smart_state_compact", "evg_check_fault", "evg_rollout_vs_policy", "evg_fog_of_war",
            "evg_sightings", "evg_smart_state", "evg_smart_actions", "evg_smart_get_action", "evg_move_table", "evg_random_actions", "evg_rollout_random", "evg_rollout_policies",
@@ -100,6 +100,18 @@ class EvgReplay(C.Structure):
         ("shared", C.c_void_p), ("swarm", C.c_void_p), ("directions", C.c_void_p), ("reward", C.c_void_p), ("meta", C.c_void_p),
         ("count", C.c_void_p), ("env_state", C.c_void_p), ("gamma_pow", C.c_void_p), ("scan", C.c_void_p), ("ctl", C.c_void_p),
     ]
+
+
+class EvgQnet(C.Structure):
+    """evg_qnet of include/evg.h: the Smart_State Q network's weights (device pointers the caller owns, nn.Linear layout), one or two sets."""
+    _fields_ = [
+        ("struct_size", C.c_uint32), ("h1", C.c_int32), ("h2", C.c_int32), ("final_relu", C.c_int32), ("num_sets", C.c_int32),
+        ("w1", C.c_void_p * 2), ("b1", C.c_void_p * 2), ("w2", C.c_void_p * 2), ("b2", C.c_void_p * 2), ("w3", C.c_void_p * 2), ("b3", C.c_void_p * 2),
+    ]
+
+
+QNET_COMPACT, QNET_COMPACT_SEATS, QNET_EXPANDED = 0, 1, 2     # EVG_QNET_*
+QNET_MAX_HIDDEN, QNET_MAX_ROWS = 64, 1 << 30
 
 
 SHAPE_NAMES = ["normalized_score", "basic_reward", "penalize_long_games", "reward_short_games", "transition", "custom"]   # index = EVG_SHAPE_*
@@ -185,6 +197,7 @@ def load(path=None):
     L.evg_replay_size.argtypes = [vp, rp, vp]
     L.evg_replay_sample.argtypes = [vp, rp, C.c_int, C.c_uint64, vp, vp, vp, vp, vp, vp, vp]
     L.evg_replay_gather.argtypes = [vp, rp, C.c_int, vp, vp, vp, vp, vp, vp, vp]
+    L.evg_smart_qnet.argtypes = [vp, C.POINTER(EvgQnet), C.c_int, C.c_int64, vp, vp, vp, vp]
     L.evg_random_actions_seat.argtypes = [vp, C.c_int, vp, vp]
     L.evg_smart_state_seat.argtypes = [vp, vp, vp, vp]
     L.evg_smart_state_compact.argtypes = [vp, C.c_int, vp, vp, vp, vp]

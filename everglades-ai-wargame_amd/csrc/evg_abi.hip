@@ -927,6 +927,34 @@ int evg_replay_gather(evg_handle* h, const evg_replay* m, int batch, const int32
     return EVG_OK;
 } catch (...) { return on_exception(); }
 
+// ---- the Smart_State Q network (include/evg.h, evg_smart_qnet) ----
+int evg_smart_qnet(evg_handle* h, const evg_qnet* net, int layout, int64_t rows, const float* in0, const float* in1, float* q_out, void* stream) try {
+    if (!h || !net) return fail(EVG_ERR_INVALID, "null handle or network descriptor");
+    if (net->struct_size != sizeof(evg_qnet)) return fail(EVG_ERR_INVALID, "qnet: struct_size %u != sizeof(evg_qnet) %zu", net->struct_size, sizeof(evg_qnet));
+    if (net->h1 < 1 || net->h1 > EVG_QNET_MAX_HIDDEN || net->h2 < 1 || net->h2 > EVG_QNET_MAX_HIDDEN)
+        return fail(EVG_ERR_INVALID, "qnet: hidden sizes must lie in 1..%d (got %d, %d)", EVG_QNET_MAX_HIDDEN, net->h1, net->h2);
+    if (net->final_relu != 0 && net->final_relu != 1) return fail(EVG_ERR_INVALID, "qnet: final_relu must be 0 or 1 (got %d)", net->final_relu);
+    if (layout != EVG_QNET_COMPACT && layout != EVG_QNET_COMPACT_SEATS && layout != EVG_QNET_EXPANDED)
+        return fail(EVG_ERR_INVALID, "qnet: unknown layout %d", layout);
+    const int sets = layout == EVG_QNET_COMPACT_SEATS ? 2 : 1;
+    if (net->num_sets != sets) return fail(EVG_ERR_INVALID, "qnet: layout %d takes %d weight set(s) (got num_sets %d)", layout, sets, net->num_sets);
+    if (rows < 1 || rows > EVG_QNET_MAX_ROWS) return fail(EVG_ERR_INVALID, "qnet: rows must lie in 1..2^30 (got %lld)", (long long)rows);
+    for (int p = 0; p < sets; ++p) {
+        const float* w[6] = {net->w1[p], net->b1[p], net->w2[p], net->b2[p], net->w3[p], net->b3[p]};
+        static const char* names[6] = {"w1", "b1", "w2", "b2", "w3", "b3"};
+        for (int i = 0; i < 6; ++i) {
+            if (!w[i]) return fail(EVG_ERR_INVALID, "qnet: %s[%d] is NULL", names[i], p);
+            if (misaligned16(w[i])) return fail(EVG_ERR_INVALID, "qnet: %s[%d] must be 16-byte aligned (got %p)", names[i], p, (const void*)w[i]);
+        }
+    }
+    if (!in0 || !q_out || (layout != EVG_QNET_EXPANDED && !in1)) return fail(EVG_ERR_INVALID, "qnet: in0, q_out and (compact layouts) in1 are required");
+    EVG_NEED_ALIGNED16(in0); EVG_NEED_ALIGNED16(in1); EVG_NEED_ALIGNED16(q_out);
+    EVG_ON_DEVICE(h);
+    const int rc = launch_smart_qnet(*net, layout, (long long)rows, in0, in1, q_out, h->caps.cus, stream);
+    if (rc) return fail(EVG_ERR_HIP, "qnet launch failed: %s", hipGetErrorString((hipError_t)rc));
+    return EVG_OK;
+} catch (...) { return on_exception(); }
+
 void evg_move_table(int32_t* table /* [11][5] */) {
     // agents/Smart_State/Move_Translation.py:3-97: node reached from (0-indexed) node n0 in direction 0 left, 1 right, 2 up, 3 down, 4 stay
     static const int32_t T[5][11] = {{1, 1, 3, 1, 2, 3, 4, 5, 6, 7, 11}, {1, 5, 6, 7, 8, 9, 10, 11, 9, 11, 11}, {2, 2, 2, 3, 5, 6, 7, 8, 8, 9, 8},

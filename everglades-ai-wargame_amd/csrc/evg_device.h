@@ -220,5 +220,7 @@ int launch_replay_count(const DevState& S, const evg_replay& m, int count_call /
 int launch_replay_draw(const DevState& S, const evg_replay& m, int batch, uint64_t seed, int32_t* handles, void* stream);
 int launch_replay_gather(const DevState& S, const evg_replay& m, int batch, const int32_t* handles, float* swarm_obs, int64_t* action, float* next_state,
                          float* reward, uint8_t* not_done, void* stream);
+// the Smart_State Q network's forward pass (qnet_kernels.inc); `net` and the sizes are validated by the caller (evg_abi.hip)
+int launch_smart_qnet(const evg_qnet& net, int layout, long long rows, const float* in0, const float* in1, float* q_out, int num_cu, void* stream);
 
 }  // namespace evg

@@ -74,6 +74,7 @@ namespace evg {
 
 #include "side_kernels.inc"     // pack, chunk-queue check, reset, seeding, action generators, fog planes, Smart_State features
 #include "replay_kernels.inc"   // the Smart_State learner's n-step replay memory: record, count, draw, gather
+#include "qnet_kernels.inc"     // the Smart_State Q network's forward pass (inference) on v_mfma_f32_16x16x4_f32
 
 // ---------------------------------------------------------------------------------------------
 // launchers

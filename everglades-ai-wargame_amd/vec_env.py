@@ -475,6 +475,13 @@ class EvergladesVecEnv(object):
         from .replay import SmartReplay
         return SmartReplay(self, capacity_turns, n_step=n_step, gamma=gamma, shaping=shaping, seats=seats, episode_base=episode_base)
 
+    def smart_qnet(self, net, final_relu=None):
+        """The Smart_State Q network's forward pass on this env's device, one launch per call (everglades_amd.SmartQNet, evg_smart_qnet): `net` is the
+        reference's QNetwork (final ReLU), an nn.Sequential Linear/ReLU/Linear/ReLU/Linear[/ReLU], a 6-tuple (w1, b1, w2, b2, w3, b3) with final_relu,
+        or a pair of these (the two-seat layout).  Its parameters are read in place on every call; the output has no autograd."""
+        from .qnet import SmartQNet
+        return SmartQNet(self, net, final_relu=final_relu)
+
     @staticmethod
     def expand_smart_state(shared, swarm):
         """[N, 12, 59] from the compact pair (for checks; a consumer would rather split its first layer's weights)."""

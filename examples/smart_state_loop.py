@@ -6,12 +6,13 @@ with everything but the network on the device, one launch each:
              --evg_smart_get_action (epsilon coin, get_random_actions / get_best_actions)--> orders [N, 7, 2] (+ directions for the replay memory)
              --evg_step_vs_policy_smart (the scripted opponent inside the step kernel)--> observation, reward, done AND the next features
 
-or, with fused=True, the last two as one launch from Q to the next features (evg_step_vs_policy_smart_q: the orders never go through HBM).
+or, with fused=True, the last two as one launch from Q to the next features (evg_step_vs_policy_smart_q: the orders never go through HBM).  With
+device_net=True the network itself runs as one launch too (env.smart_qnet: evg_smart_qnet on the compact features, the same weights read in place).
 
 The network here is a stand-in with random weights, evaluated on the COMPACT features: features[e, s] = cat(shared[e], swarm[e, s], onehot(s)), so the first
 layer is W[:, :34] @ shared + W[:, 34:47] @ swarm + W[:, 47 + s] -- a quarter of the bytes of the expanded [N, 12, 59] matrix.
 
-    python examples/smart_state_loop.py [envs] [turns] [epsilon] [fused]
+    python examples/smart_state_loop.py [envs] [turns] [epsilon] [fused] [device_net]
 """
 import os
 import sys
@@ -35,12 +36,16 @@ def make_network(device, seed=0):
         h = torch.relu(h)
         h = torch.relu(h @ w2.T + b2)
         return (h @ w3.T + b3).contiguous()                          # [N, 12, 5]
+    q_values.params = (w1, b1, w2, b2, w3, b3)                        # nn.Linear layout, no final ReLU: what env.smart_qnet(..., final_relu=False) reads
     return q_values
 
 
-def main(num_envs=8192, turns=200, epsilon=0.1, opponent="swarm_agent", seat=0, seed=1, fused=False):
+def main(num_envs=8192, turns=200, epsilon=0.1, opponent="swarm_agent", seat=0, seed=1, fused=False, device_net=False):
     env = evg.EvergladesVecEnv(num_envs, seed=seed, auto_reset=True)
     net = make_network(env.device)
+    if device_net:       # the same network as one launch (evg_smart_qnet), into one Q buffer
+        qnet, qbuf = env.smart_qnet(net.params, final_relu=False), torch.empty((num_envs, 12, 5), device=env.device)
+        net = lambda shared, swarm: qnet(shared, swarm, out=qbuf)     # noqa: E731
     env.reset()
     obs = env.observe_seat(seat)                                      # [N, 105]
     shared, swarm = env.smart_state_compact(-1, obs)                  # the first features of the loop; afterwards the step launch refills them
@@ -67,4 +72,5 @@ def main(num_envs=8192, turns=200, epsilon=0.1, opponent="swarm_agent", seat=0, 
 
 if __name__ == "__main__":
     a = sys.argv[1:]
-    main(int(a[0]) if a else 8192, int(a[1]) if len(a) > 1 else 200, float(a[2]) if len(a) > 2 else 0.1, fused=len(a) > 3 and a[3] in ("1", "fused"))
+    main(int(a[0]) if a else 8192, int(a[1]) if len(a) > 1 else 200, float(a[2]) if len(a) > 2 else 0.1, fused=len(a) > 3 and a[3] in ("1", "fused"),
+         device_net=len(a) > 4 and a[4] in ("1", "device_net"))

@@ -10,9 +10,10 @@ fused=True, one launch per turn from both seats' Q values to both players' next 
 fused=False, the same turn as separate calls: evg_smart_get_action for seat 0 and for seat 1, evg_step with both seats' rows (stacked into [N, 2, 7, 2]),
 evg_smart_state_compact for player 0 and for player 1.
 
-The networks are stand-ins with random weights (examples/smart_state_loop.py's make_network, two seeds) evaluated on the compact features.
+The networks are stand-ins with random weights (examples/smart_state_loop.py's make_network, two seeds) evaluated on the compact features; with
+device_net=True by env.smart_qnet (evg_smart_qnet): fused, both seats' networks in one launch on [N, 2, ...]; otherwise one launch per seat.
 
-    python examples/smart_state_self_play.py [envs] [turns] [fused]
+    python examples/smart_state_self_play.py [envs] [turns] [fused] [device_net]
 """
 import os
 import sys
@@ -25,10 +26,14 @@ import everglades_amd as evg
 from smart_state_loop import make_network
 
 
-def main(num_envs=8192, turns=200, epsilon=(0.1, 0.0), seed=1, fused=False):
+def main(num_envs=8192, turns=200, epsilon=(0.1, 0.0), seed=1, fused=False, device_net=False):
     env = evg.EvergladesVecEnv(num_envs, seed=seed, auto_reset=True)
     nets = (make_network(env.device, seed=0), make_network(env.device, seed=1))
     dev = env.device
+    if device_net:
+        pair = env.smart_qnet((nets[0].params, nets[1].params), final_relu=False)     # both seats, one launch
+        qbuf = torch.empty((num_envs, 2, 12, 5), device=dev)
+        nets = tuple((lambda q: (lambda shared, swarm: q(shared, swarm)))(env.smart_qnet(n.params, final_relu=False)) for n in nets)
     obs = env.reset()                                                 # [N, 2, 105]
     if fused:
         shared = torch.empty((num_envs, 2, 34), device=dev)
@@ -50,7 +55,10 @@ def main(num_envs=8192, turns=200, epsilon=(0.1, 0.0), seed=1, fused=False):
     t0 = time.perf_counter()
     for _ in range(turns):
         if fused:            # one launch: both seats' orders are decoded from q inside the step (evg_step_smart_q)
-            q = torch.stack([nets[p](feats[p][0].contiguous(), feats[p][1].contiguous()) for p in range(2)], dim=1)     # [N, 2, 12, 5]
+            if device_net:
+                q = pair(shared, swarm, out=qbuf)
+            else:
+                q = torch.stack([nets[p](feats[p][0].contiguous(), feats[p][1].contiguous()) for p in range(2)], dim=1)     # [N, 2, 12, 5]
             obs, reward, done, info = env.step_q(q, epsilon, features=(shared, swarm), directions=directions, explored=explored)
         else:
             for p in range(2):
@@ -70,4 +78,5 @@ def main(num_envs=8192, turns=200, epsilon=(0.1, 0.0), seed=1, fused=False):
 
 if __name__ == "__main__":
     a = sys.argv[1:]
-    main(int(a[0]) if a else 8192, int(a[1]) if len(a) > 1 else 200, fused=len(a) > 2 and a[2] in ("1", "fused"))
+    main(int(a[0]) if a else 8192, int(a[1]) if len(a) > 1 else 200, fused=len(a) > 2 and a[2] in ("1", "fused"),
+         device_net=len(a) > 3 and a[3] in ("1", "device_net"))

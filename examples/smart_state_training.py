@@ -10,7 +10,11 @@ reward_shaping.reward_short_games + remember_game_state + end_of_episode's n-ste
 The network is the reference's QNetwork shape (59-60-60-5, relu) with random weights; the loss is F.smooth_l1_loss of the reference, the target the mean
 over swarms of the best target-network Q of the next state, times gamma ** n_step, plus the n-step reward.  A DQN loss need not decrease.
 
-    python examples/smart_state_training.py [envs] [turns] [batch]
+With device_net=True the acting forward (policy on the compact features) and the target network's forward on sample()'s next_state_swarms run as
+one launch each (env.smart_qnet, evg_smart_qnet: the modules' parameters read in place, so Adam's steps and load_state_dict are seen); the policy
+forward inside optimize_model stays torch (its gradient is the loss's).
+
+    python examples/smart_state_training.py [envs] [turns] [batch] [device_net]
 """
 import os
 import sys
@@ -34,12 +38,12 @@ def q_values(net, shared, swarm):
     return net(evg.EvergladesVecEnv.expand_smart_state(shared, swarm)).contiguous()
 
 
-def optimize_model(policy, target, opt, batch):
-    """DQNAgent.optimize_model (DQNAgent.py:336-385) on the sampled operands."""
+def optimize_model(policy, target, opt, batch, target_eval=None):
+    """DQNAgent.optimize_model (DQNAgent.py:336-385) on the sampled operands.  target_eval: the target network on the device (SmartQNet.expanded)."""
     swarm_obs, action, next_state, reward, not_done = batch
     predicted = policy(swarm_obs).gather(1, action.unsqueeze(1))
     with torch.no_grad():
-        nxt = target(next_state)                                       # [B, 12, 5]; zeros rows where not_done is False give Q of zeros: mask below
+        nxt = target(next_state) if target_eval is None else target_eval(next_state)                                       # [B, 12, 5]; zeros rows where not_done is False give Q of zeros: mask below
         nxt = torch.where(not_done[:, None, None], nxt, torch.zeros_like(nxt))
         future = nxt.amax(2).mean(1)
         estimated = future * (GAMMA ** N_STEP) + reward
@@ -52,12 +56,15 @@ def optimize_model(policy, target, opt, batch):
     return loss.detach()
 
 
-def main(num_envs=8192, turns=300, batch=1024, opponent="swarm_agent", seat=0, seed=1, epsilon=0.3):
+def main(num_envs=8192, turns=300, batch=1024, opponent="swarm_agent", seat=0, seed=1, epsilon=0.3, device_net=False):
     env = evg.EvergladesVecEnv(num_envs, seed=seed, auto_reset=True)
     dev = env.device
     policy, target = make_qnet(dev, 0), make_qnet(dev, 0)
     target.load_state_dict(policy.state_dict())
     opt = torch.optim.Adam(policy.parameters(), lr=LR)
+    act_net = target_eval = None
+    if device_net:
+        act_net, target_eval = env.smart_qnet(policy), env.smart_qnet(target).expanded
     mem = env.smart_replay(8, n_step=N_STEP, gamma=GAMMA, shaping="reward_short_games", seats=seat)
     env.reset()
     env.smart_state_compact(-1, env.observe_seat(seat), *mem.slot_features(0))   # record 0's features
@@ -66,11 +73,11 @@ def main(num_envs=8192, turns=300, batch=1024, opponent="swarm_agent", seat=0, s
     t0 = time.perf_counter()
     for t in range(turns):
         with torch.no_grad():
-            q = q_values(policy, *mem.slot_features(t))
+            q = q_values(policy, *mem.slot_features(t)) if act_net is None else act_net(*mem.slot_features(t))
         env.step_vs_q(opponent, q, epsilon, seat=seat, features=mem.slot_features(t + 1), directions=mem.slot_directions(t))
         mem.record()
         if t >= N_STEP + 1:
-            losses.append(optimize_model(policy, target, opt, mem.sample(batch, seed=seed)))
+            losses.append(optimize_model(policy, target, opt, mem.sample(batch, seed=seed), target_eval))
         if t % 100 == 99:
             target.load_state_dict(policy.state_dict())
     torch.cuda.synchronize()
@@ -86,4 +93,4 @@ def main(num_envs=8192, turns=300, batch=1024, opponent="swarm_agent", seat=0, s
 
 if __name__ == "__main__":
     a = sys.argv[1:]
-    main(int(a[0]) if a else 8192, int(a[1]) if len(a) > 1 else 300, int(a[2]) if len(a) > 2 else 1024)
+    main(int(a[0]) if a else 8192, int(a[1]) if len(a) > 1 else 300, int(a[2]) if len(a) > 2 else 1024, device_net=len(a) > 3 and a[3] in ("1", "device_net"))

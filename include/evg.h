@@ -38,7 +38,8 @@ extern "C" {
 
 #define EVG_ABI_VERSION 7
 /* 7: evg_step_vs_policy_smart_q (the Smart_State learner's turn from its Q values: DQNAgent.get_action decoded inside the learner-seat step launch);
- *    evg_step_smart_q (the self-play turn: both seats' Q values decoded inside one step launch; an added function, no layout changed) */
+ *    evg_step_smart_q (the self-play turn: both seats' Q values decoded inside one step launch; an added function, no layout changed);
+ *    evg_smart_qnet with its descriptor evg_qnet: the Smart_State Q network's forward pass in one launch (added, no layout changed) */
 /* 6: evg_smart_get_action (DQNAgent.get_action with epsilon > 0), evg_step_vs_policy_smart (the learner-seat turn that also writes the Smart_State
  *    features), evg_get_run_state / evg_set_run_state (agent objects, returns, win counters: checkpoint / resume); reward / score buffers need 8-byte
  *    alignment only (5 asked 16 of every buffer)
@@ -611,6 +612,39 @@ EVG_API int evg_replay_sample(evg_handle* h, const evg_replay* m, int batch, uin
  * EVG_REPLAY_S_BAD_HANDLE in ctl[1]. */
 EVG_API int evg_replay_gather(evg_handle* h, const evg_replay* m, int batch, const int32_t* handles, float* swarm_obs, int64_t* action, float* next_state,
                               float* reward, uint8_t* not_done, void* stream);
+
+/* ---- The Smart_State Q network, inference only (agents/Smart_State/QNetwork.py: relu(fc3(relu(fc2(relu(fc1(x))))))) ------------------------------
+ * The consumer's network stays the consumer's: its weights are its own fp32 tensors (nn.Linear layout, contiguous, 16-byte aligned), read in place on
+ * every call, so an optimizer step or a load_state_dict takes effect without rebinding.  Training (autograd, the optimizer) stays with the consumer.
+ *   set p:   w1[p] [h1][59], b1[p] [h1], w2[p] [h2][h1], b2[p] [h2], w3[p] [5][h2], b3[p] [5]           h1, h2 in 1..64
+ * Numerics (bit-exact, reproducible by a host model): every pre-activation is acc = b[j], then acc = fmaf(W[j][k], x[k], acc) for k ascending over the
+ * layer's input index; then fmaxf(acc, 0) on the two hidden layers, and on the output layer when final_relu is set (the reference's QNetwork applies
+ * it).  Input row of a compact layout: x = shared(34) ++ swarm[s](13) ++ onehot(s)(12); the chain's prefix b1[j] + the 34 shared terms is computed once
+ * per env and continued per swarm, the one-hot term at position 47 + s is acc + w1[j][47 + s] (a zero term leaves the chain unchanged), so the compact
+ * and the expanded layouts give equal Q for the same features.
+ * Layouts (rows R; any R >= 1 up to 2^30, independent of the handle's N: the handle only names the device):
+ *   EVG_QNET_COMPACT        in0 = shared [R][34], in1 = swarm [R][12][13]        -> q_out [R][12][5]     (num_sets 1)
+ *   EVG_QNET_COMPACT_SEATS  in0 = shared [R][2][34], in1 = swarm [R][2][12][13]  -> q_out [R][2][12][5]  (num_sets 2: seat p uses set p)
+ *   EVG_QNET_EXPANDED       in0 = x [R][59], in1 = NULL                          -> q_out [R][5]         (num_sets 1)
+ * One launch on `stream`, no synchronisation, nothing allocated.  Refused with EVG_ERR_INVALID (nothing launched): struct_size != sizeof(evg_qnet), h1 or
+ * h2 outside 1..64, final_relu not 0/1, an unknown layout, a num_sets the layout does not take, a NULL or not 16-byte aligned pointer, R outside 1..2^30.
+ * The output is a plain tensor of values: gradients of the network (optimize_model's policy forward) stay with the consumer. */
+enum { EVG_QNET_COMPACT = 0, EVG_QNET_COMPACT_SEATS = 1, EVG_QNET_EXPANDED = 2 };
+#define EVG_QNET_MAX_HIDDEN 64
+#define EVG_QNET_MAX_ROWS (1LL << 30)
+typedef struct evg_qnet {
+    uint32_t struct_size;          /* sizeof(evg_qnet)                                                                      */
+    int32_t h1, h2;                /* hidden sizes, 1..64 (fc1_size / fc2_size of the reference's pickles; default 60 / 60)  */
+    int32_t final_relu;            /* 0 / 1: fmaxf(q, 0) on the output layer                                                */
+    int32_t num_sets;              /* 1, or 2 for EVG_QNET_COMPACT_SEATS                                                    */
+    const float* w1[2];
+    const float* b1[2];
+    const float* w2[2];
+    const float* b2[2];
+    const float* w3[2];
+    const float* b3[2];
+} evg_qnet;
+EVG_API int evg_smart_qnet(evg_handle* h, const evg_qnet* net, int layout, int64_t rows, const float* in0, const float* in1, float* q_out, void* stream);
 
 #ifdef __cplusplus
 }
