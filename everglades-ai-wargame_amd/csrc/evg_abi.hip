@@ -124,20 +124,43 @@ struct evg_handle {
 #endif
 };
 
-// arguments of one step-kernel launch
-static StepIO make_io(const evg_handle* h, const int32_t* actions, void* obs, float* reward, uint8_t* done, int8_t* winner, int32_t* scores,
-                      uint8_t* status, int observe_only, int gen_actions, int policy0, int policy1, int32_t* actions_out) {
-    StepIO io;
-    memset(&io, 0, sizeof(io));
-    io.actions = actions; io.obs = obs; io.reward = reward; io.done = done; io.winner = winner; io.scores = scores; io.status = status;
-    io.observe_only = observe_only; io.gen_actions = gen_actions; io.policy0 = policy0; io.policy1 = policy1; io.actions_out = actions_out;
-    io.turns = 1;
+// Arguments of one step-kernel launch: everything zero / NULL ("not given") and one turn; the entry point assigns the fields it means, by name.  The
+// diagnostic libraries' knobs come from the handle; a launch that only rebuilds observations is neither ablated nor stamped.
+struct LaunchIO : StepIO {
+    explicit LaunchIO(const evg_handle* h, bool observe_only_launch = false) {
+        memset(static_cast<StepIO*>(this), 0, sizeof(StepIO));
+        turns = 1;
+        observe_only = observe_only_launch ? 1 : 0;
 #ifdef EVG_DIAG
-    io.lanes_per_wave = h->lanes; io.ablate = observe_only ? 0u : h->ablate; io.stamps = observe_only ? nullptr : h->stamps;
+        lanes_per_wave = h->lanes; ablate = observe_only ? 0u : h->ablate; stamps = observe_only ? nullptr : h->stamps;
 #else
-    (void)h;
+        (void)h;
 #endif
-    return io;
+    }
+};
+
+// the end of an entry point that enqueues: the launchers return the hipError_t of their own launch (0 = success)
+static int launched(const char* what, int rc) {
+    if (rc) return fail(EVG_ERR_HIP, "%s%slaunch failed: %s", what, *what ? " " : "", hipGetErrorString((hipError_t)rc));
+    return EVG_OK;
+}
+
+// argument checks the step family shares (each entry point runs them in its own order: the first failing check decides the message)
+static int check_seat_and_opponent(int seat, int opponent_policy) {
+    if (seat < 0 || seat > 1 || opponent_policy < 0 || opponent_policy >= EVG_POLICY_COUNT) return fail(EVG_ERR_INVALID, "seat / opponent_policy out of range");
+    return EVG_OK;
+}
+static int check_keyed_philox(const evg_handle* h, const char* entry, const char* why = "") {
+    if (h->S.mt_key) return fail(EVG_ERR_INVALID, "%s: keyed-Philox handles only%s", entry, why);
+    return EVG_OK;
+}
+static int check_epsilon(float epsilon, const float* epsilon_env) {
+    if (!epsilon_env && !(epsilon >= 0.0f && epsilon <= 1.0f)) return fail(EVG_ERR_INVALID, "epsilon %g outside [0, 1]", (double)epsilon);
+    return EVG_OK;
+}
+static int check_feature_pair(const float* shared_out, const float* swarm_out) {
+    if (!shared_out != !swarm_out) return fail(EVG_ERR_INVALID, "shared_out and swarm_out are both NULL or both set");
+    return EVG_OK;
 }
 
 template <typename Tp>
@@ -168,11 +191,19 @@ static int check_fault(evg_handle* h, uint32_t* word_out = nullptr) {
     return EVG_OK;
 }
 
+// The key of the graph cache: every field of StepIO that the caller owns (the launcher-owned ones -- env_lo, env_hi, flags, nsets, chunk_turns, grid_slots,
+// progress_base -- are set by launch_step inside the captured plan).  A new field of StepIO changes its size: visit same_launch, then the number.
+#ifdef EVG_DIAG
+static_assert(sizeof(StepIO) == 200, "StepIO changed (diagnostic layout): visit same_launch");
+#else
+static_assert(sizeof(StepIO) == 184, "StepIO changed: visit same_launch");
+#endif
 static bool same_launch(const StepIO& a, const StepIO& b) {
     bool same = a.actions == b.actions && a.obs == b.obs && a.reward == b.reward && a.done == b.done && a.winner == b.winner && a.scores == b.scores &&
                 a.status == b.status && a.observe_only == b.observe_only && a.gen_actions == b.gen_actions && a.policy0 == b.policy0 &&
                 a.policy1 == b.policy1 && a.actions_out == b.actions_out && a.turns == b.turns && a.seat == b.seat && a.actions_both == b.actions_both &&
-                a.feat_shared == b.feat_shared && a.feat_swarm == b.feat_swarm;
+                a.feat_shared == b.feat_shared && a.feat_swarm == b.feat_swarm && a.q == b.q && a.eps == b.eps && a.eps1 == b.eps1 &&
+                a.eps_env == b.eps_env && a.q_actions == b.q_actions && a.q_directions == b.q_directions && a.q_explored == b.q_explored;
 #ifdef EVG_DIAG
     same = same && a.lanes_per_wave == b.lanes_per_wave && a.ablate == b.ablate && a.stamps == b.stamps;
 #endif
@@ -225,6 +256,32 @@ static int launch_rollout(evg_handle* h, const StepIO& io, hipStream_t s) {
     hipGraphExec_t exec = caller_captures ? nullptr : graph_of(h, io);
     if (!exec) return launch_step(h->S, io, h->cfg.obs_dtype, h->caps, s);
     return (int)hipGraphLaunch(exec, s);
+}
+
+// One launch per turn: the loop is timed as a whole with two events on the stream (an event pair around every launch would
+// make the queue wait for each bracketed kernel to retire and stretch what it measures): step_kernel_ms is the stream
+// time per turn -- the step kernel, the gap to the next launch and, when the orders are not drawn by the step kernel
+// itself (fused == 0), the action kernel(s) of the turn.  The kernel alone is in the rocprofv3 traces under profiles/.
+// `turn` enqueues one turn and returns EVG_OK or what the call is to fail with.
+template <typename Turn>
+static int timed_turns(evg_handle* h, int steps, float* step_kernel_ms, hipStream_t s_, Turn&& turn) {
+    while (step_kernel_ms && h->events.size() < 2) {
+        hipEvent_t ev;
+        HIP_TRY(hipEventCreate(&ev));
+        h->events.push_back(ev);
+    }
+    if (step_kernel_ms) HIP_TRY(hipEventRecord(h->events[0], s_));
+    for (int i = 0; i < steps; ++i)
+        if (const int rc = turn()) return rc;
+    if (step_kernel_ms) {
+        HIP_TRY(hipEventRecord(h->events[1], s_));
+        HIP_TRY(hipStreamSynchronize(s_));
+        float ms = 0.f;
+        HIP_TRY(hipEventElapsedTime(&ms, h->events[0], h->events[1]));
+        *step_kernel_ms = ms / (float)steps;
+        return check_fault(h);
+    }
+    return EVG_OK;
 }
 
 // "No C++ exception crosses the ABI" (include/evg.h): every int-returning entry point below is a function-try-block that ends here.  The only exceptions the
@@ -631,9 +688,7 @@ int evg_reset(evg_handle* h, const uint8_t* mask, void* obs_out, void* stream) t
     if (!h) return fail(EVG_ERR_INVALID, "null handle");
     EVG_NEED_ALIGNED16(obs_out);
     EVG_ON_DEVICE(h);
-    const int rc = launch_reset(h->S, mask, obs_out, h->cfg.obs_dtype, stream);
-    if (rc) return fail(EVG_ERR_HIP, "reset launch failed: %s", hipGetErrorString((hipError_t)rc));
-    return EVG_OK;
+    return launched("reset", launch_reset(h->S, mask, obs_out, h->cfg.obs_dtype, stream));
 } catch (...) { return on_exception(); }
 
 int evg_step(evg_handle* h, const int32_t* actions, void* obs_out, float* reward_out, uint8_t* done_out, int8_t* winner_out,
@@ -642,20 +697,19 @@ int evg_step(evg_handle* h, const int32_t* actions, void* obs_out, float* reward
     if (!actions || !reward_out || !done_out) return fail(EVG_ERR_INVALID, "actions, reward_out and done_out are required");
     EVG_NEED_ALIGNED16(actions); EVG_NEED_ALIGNED16(obs_out); EVG_NEED_ALIGNED8(reward_out); EVG_NEED_ALIGNED8(scores_out);
     EVG_ON_DEVICE(h);
-    const StepIO io = make_io(h, actions, obs_out, reward_out, done_out, winner_out, scores_out, status_out, 0, 0, 0, 0, nullptr);
-    const int rc = launch_step(h->S, io, h->cfg.obs_dtype, h->caps, stream);
-    if (rc) return fail(EVG_ERR_HIP, "step launch failed: %s", hipGetErrorString((hipError_t)rc));
-    return EVG_OK;
+    LaunchIO io(h);
+    io.actions = actions; io.obs = obs_out;
+    io.reward = reward_out; io.done = done_out; io.winner = winner_out; io.scores = scores_out; io.status = status_out;
+    return launched("step", launch_step(h->S, io, h->cfg.obs_dtype, h->caps, stream));
 } catch (...) { return on_exception(); }
 
 int evg_observe(evg_handle* h, void* obs_out, void* stream) try {
     if (!h || !obs_out) return fail(EVG_ERR_INVALID, "null argument");
     EVG_NEED_ALIGNED16(obs_out);
     EVG_ON_DEVICE(h);
-    const StepIO io = make_io(h, nullptr, obs_out, nullptr, nullptr, nullptr, nullptr, nullptr, 1, 0, 0, 0, nullptr);
-    const int rc = launch_step(h->S, io, h->cfg.obs_dtype, h->caps, stream);
-    if (rc) return fail(EVG_ERR_HIP, "observe launch failed: %s", hipGetErrorString((hipError_t)rc));
-    return EVG_OK;
+    LaunchIO io(h, /* observe_only_launch */ true);
+    io.obs = obs_out;
+    return launched("observe", launch_step(h->S, io, h->cfg.obs_dtype, h->caps, stream));
 } catch (...) { return on_exception(); }
 
 static int step_vs_policy_impl(evg_handle* h, int seat, const int32_t* actions, int actions_both_seats, int opponent_policy, void* obs_seat_out,
@@ -663,17 +717,18 @@ static int step_vs_policy_impl(evg_handle* h, int seat, const int32_t* actions, 
                                uint8_t* status_out, void* stream) {
     if (!h) return fail(EVG_ERR_INVALID, "null handle");
     if (!actions || !obs_seat_out || !reward_out || !done_out) return fail(EVG_ERR_INVALID, "actions, obs_seat_out, reward_out and done_out are required");
-    if (seat < 0 || seat > 1 || opponent_policy < 0 || opponent_policy >= EVG_POLICY_COUNT) return fail(EVG_ERR_INVALID, "seat / opponent_policy out of range");
+    if (const int rc = check_seat_and_opponent(seat, opponent_policy)) return rc;
     EVG_NEED_ALIGNED16(obs_seat_out); EVG_NEED_ALIGNED16(actions); EVG_NEED_ALIGNED8(reward_out); EVG_NEED_ALIGNED8(scores_out);
     EVG_NEED_ALIGNED8(shared_out); EVG_NEED_ALIGNED16(swarm_out);
-    if (h->S.mt_key) return fail(EVG_ERR_INVALID, "evg_step_vs_policy: keyed-Philox handles only (the stock-entropy mode has no fused bots)");
+    if (const int rc = check_keyed_philox(h, "evg_step_vs_policy", " (the stock-entropy mode has no fused bots)")) return rc;
     EVG_ON_DEVICE(h);
-    StepIO io = make_io(h, actions, obs_seat_out, reward_out, done_out, winner_out, scores_out, status_out, 0, 2, opponent_policy, opponent_policy, nullptr);
+    LaunchIO io(h);
+    io.actions = actions; io.obs = obs_seat_out;
+    io.reward = reward_out; io.done = done_out; io.winner = winner_out; io.scores = scores_out; io.status = status_out;
+    io.gen_actions = 2; io.policy0 = io.policy1 = opponent_policy;
     io.seat = seat; io.actions_both = actions_both_seats ? 1 : 0;
     io.feat_shared = shared_out; io.feat_swarm = swarm_out;
-    const int rc = launch_step_seat(h->S, io, h->cfg.obs_dtype, h->caps, stream);
-    if (rc) return fail(EVG_ERR_HIP, "step launch failed: %s", hipGetErrorString((hipError_t)rc));
-    return EVG_OK;
+    return launched("step", launch_step_seat(h->S, io, h->cfg.obs_dtype, h->caps, stream));
 }
 
 int evg_step_vs_policy(evg_handle* h, int seat, const int32_t* actions, int actions_both_seats, int opponent_policy, void* obs_seat_out, float* reward_out,
@@ -695,22 +750,23 @@ int evg_step_vs_policy_smart_q(evg_handle* h, int seat, const float* q, float ep
                                uint8_t* done_out, int8_t* winner_out, int32_t* scores_out, uint8_t* status_out, void* stream) try {
     if (!h) return fail(EVG_ERR_INVALID, "null handle");
     if (!q || !obs_seat_out || !reward_out || !done_out) return fail(EVG_ERR_INVALID, "q, obs_seat_out, reward_out and done_out are required");
-    if (seat < 0 || seat > 1 || opponent_policy < 0 || opponent_policy >= EVG_POLICY_COUNT) return fail(EVG_ERR_INVALID, "seat / opponent_policy out of range");
-    if (!epsilon_env && !(epsilon >= 0.0f && epsilon <= 1.0f)) return fail(EVG_ERR_INVALID, "epsilon %g outside [0, 1]", (double)epsilon);
-    if (!shared_out != !swarm_out) return fail(EVG_ERR_INVALID, "shared_out and swarm_out are both NULL or both set");
+    if (const int rc = check_seat_and_opponent(seat, opponent_policy)) return rc;
+    if (const int rc = check_epsilon(epsilon, epsilon_env)) return rc;
+    if (const int rc = check_feature_pair(shared_out, swarm_out)) return rc;
     // (the fused feature store writes shared_out as float4 for every whole wavefront: 16 bytes, not the 8 evg_smart_state_compact needs)
     EVG_NEED_ALIGNED16(q); EVG_NEED_ALIGNED16(obs_seat_out); EVG_NEED_ALIGNED16(shared_out); EVG_NEED_ALIGNED16(swarm_out);
     EVG_NEED_ALIGNED16(actions_out); EVG_NEED_ALIGNED16(directions_out); EVG_NEED_ALIGNED8(reward_out); EVG_NEED_ALIGNED8(scores_out);
-    if (h->S.mt_key) return fail(EVG_ERR_INVALID, "evg_step_vs_policy_smart_q: keyed-Philox handles only (the stock-entropy mode has no fused bots)");
+    if (const int rc = check_keyed_philox(h, "evg_step_vs_policy_smart_q", " (the stock-entropy mode has no fused bots)")) return rc;
     EVG_ON_DEVICE(h);
-    StepIO io = make_io(h, nullptr, obs_seat_out, reward_out, done_out, winner_out, scores_out, status_out, 0, 2, opponent_policy, opponent_policy, nullptr);
+    LaunchIO io(h);
+    io.obs = obs_seat_out;
+    io.reward = reward_out; io.done = done_out; io.winner = winner_out; io.scores = scores_out; io.status = status_out;
+    io.gen_actions = 2; io.policy0 = io.policy1 = opponent_policy;
     io.seat = seat;
     io.feat_shared = shared_out; io.feat_swarm = swarm_out;
     io.q = q; io.eps = epsilon; io.eps_env = epsilon_env;
     io.q_actions = actions_out; io.q_directions = directions_out; io.q_explored = explored_out;
-    const int rc = launch_step_seat(h->S, io, h->cfg.obs_dtype, h->caps, stream);
-    if (rc) return fail(EVG_ERR_HIP, "step launch failed: %s", hipGetErrorString((hipError_t)rc));
-    return EVG_OK;
+    return launched("step", launch_step_seat(h->S, io, h->cfg.obs_dtype, h->caps, stream));
 } catch (...) { return on_exception(); }
 
 int evg_step_smart_q(evg_handle* h, const float* q, float epsilon0, float epsilon1, const float* epsilon_env, void* obs_out, float* shared_out, float* swarm_out,
@@ -720,49 +776,43 @@ int evg_step_smart_q(evg_handle* h, const float* q, float epsilon0, float epsilo
     if (!q || !obs_out || !reward_out || !done_out) return fail(EVG_ERR_INVALID, "q, obs_out, reward_out and done_out are required");
     if (!epsilon_env && !(epsilon0 >= 0.0f && epsilon0 <= 1.0f && epsilon1 >= 0.0f && epsilon1 <= 1.0f))
         return fail(EVG_ERR_INVALID, "epsilon0 %g / epsilon1 %g outside [0, 1]", (double)epsilon0, (double)epsilon1);
-    if (!shared_out != !swarm_out) return fail(EVG_ERR_INVALID, "shared_out and swarm_out are both NULL or both set");
+    if (const int rc = check_feature_pair(shared_out, swarm_out)) return rc;
     // (the fused feature store writes shared_out and swarm_out as float4)
     EVG_NEED_ALIGNED16(q); EVG_NEED_ALIGNED16(obs_out); EVG_NEED_ALIGNED16(shared_out); EVG_NEED_ALIGNED16(swarm_out);
     EVG_NEED_ALIGNED16(actions_out); EVG_NEED_ALIGNED16(directions_out); EVG_NEED_ALIGNED8(reward_out); EVG_NEED_ALIGNED8(scores_out);
-    if (h->S.mt_key) return fail(EVG_ERR_INVALID, "evg_step_smart_q: keyed-Philox handles only (the stock-entropy mode has no fused decode)");
+    if (const int rc = check_keyed_philox(h, "evg_step_smart_q", " (the stock-entropy mode has no fused decode)")) return rc;
     EVG_ON_DEVICE(h);
-    StepIO io = make_io(h, nullptr, obs_out, reward_out, done_out, winner_out, scores_out, status_out, 0, 0, 0, 0, nullptr);
+    LaunchIO io(h);
+    io.obs = obs_out;
+    io.reward = reward_out; io.done = done_out; io.winner = winner_out; io.scores = scores_out; io.status = status_out;
     io.feat_shared = shared_out; io.feat_swarm = swarm_out;
     io.q = q; io.eps = epsilon0; io.eps1 = epsilon1; io.eps_env = epsilon_env;
     io.q_actions = actions_out; io.q_directions = directions_out; io.q_explored = explored_out;
-    const int rc = launch_step_smart_q(h->S, io, h->cfg.obs_dtype, h->caps, stream);
-    if (rc) return fail(EVG_ERR_HIP, "step launch failed: %s", hipGetErrorString((hipError_t)rc));
-    return EVG_OK;
+    return launched("step", launch_step_smart_q(h->S, io, h->cfg.obs_dtype, h->caps, stream));
 } catch (...) { return on_exception(); }
 
 int evg_observe_seat(evg_handle* h, int seat, void* obs_seat_out, void* stream) try {
     if (!h || !obs_seat_out || seat < 0 || seat > 1) return fail(EVG_ERR_INVALID, "bad argument");
     EVG_NEED_ALIGNED16(obs_seat_out);
-    if (h->S.mt_key) return fail(EVG_ERR_INVALID, "evg_observe_seat: keyed-Philox handles only");
+    if (const int rc = check_keyed_philox(h, "evg_observe_seat")) return rc;
     EVG_ON_DEVICE(h);
-    StepIO io = make_io(h, nullptr, obs_seat_out, nullptr, nullptr, nullptr, nullptr, nullptr, 1, 0, 0, 0, nullptr);
-    io.seat = seat;
-    const int rc = launch_step_seat(h->S, io, h->cfg.obs_dtype, h->caps, stream);
-    if (rc) return fail(EVG_ERR_HIP, "observe launch failed: %s", hipGetErrorString((hipError_t)rc));
-    return EVG_OK;
+    LaunchIO io(h, /* observe_only_launch */ true);
+    io.obs = obs_seat_out; io.seat = seat;
+    return launched("observe", launch_step_seat(h->S, io, h->cfg.obs_dtype, h->caps, stream));
 } catch (...) { return on_exception(); }
 
 int evg_random_actions(evg_handle* h, int32_t* actions_out, void* stream) try {
     if (!h || !actions_out) return fail(EVG_ERR_INVALID, "null argument");
     EVG_NEED_ALIGNED16(actions_out);
     EVG_ON_DEVICE(h);
-    const int rc = launch_random_actions(h->S, actions_out, -1, stream);
-    if (rc) return fail(EVG_ERR_HIP, "random_actions launch failed: %s", hipGetErrorString((hipError_t)rc));
-    return EVG_OK;
+    return launched("random_actions", launch_random_actions(h->S, actions_out, -1, stream));
 } catch (...) { return on_exception(); }
 
 int evg_random_actions_seat(evg_handle* h, int seat, int32_t* actions_seat_out, void* stream) try {
     if (!h || !actions_seat_out || seat < 0 || seat > 1) return fail(EVG_ERR_INVALID, "bad argument");
     EVG_NEED_ALIGNED16(actions_seat_out);
     EVG_ON_DEVICE(h);
-    const int rc = launch_random_actions(h->S, actions_seat_out, seat, stream);
-    if (rc) return fail(EVG_ERR_HIP, "random_actions launch failed: %s", hipGetErrorString((hipError_t)rc));
-    return EVG_OK;
+    return launched("random_actions", launch_random_actions(h->S, actions_seat_out, seat, stream));
 } catch (...) { return on_exception(); }
 
 int evg_scripted_actions(evg_handle* h, int policy, int player, const void* obs, int32_t* actions_out, void* stream) try {
@@ -770,74 +820,58 @@ int evg_scripted_actions(evg_handle* h, int policy, int player, const void* obs,
     if (policy < 0 || policy >= EVG_POLICY_COUNT || player < 0 || player > 1) return fail(EVG_ERR_INVALID, "policy/player out of range");
     EVG_NEED_ALIGNED16(obs); EVG_NEED_ALIGNED16(actions_out);
     EVG_ON_DEVICE(h);
-    const int rc = launch_scripted_actions(h->S, policy, player, obs, actions_out, h->cfg.obs_dtype, stream);
-    if (rc) return fail(EVG_ERR_HIP, "scripted_actions launch failed: %s", hipGetErrorString((hipError_t)rc));
-    return EVG_OK;
+    return launched("scripted_actions", launch_scripted_actions(h->S, policy, player, obs, actions_out, h->cfg.obs_dtype, stream));
 } catch (...) { return on_exception(); }
 
 int evg_fog_of_war(evg_handle* h, uint8_t* fog_out, uint8_t* knowledge_out, void* stream) try {
     if (!h || (!fog_out && !knowledge_out)) return fail(EVG_ERR_INVALID, "null argument");
     EVG_ON_DEVICE(h);
-    const int rc = launch_fog(h->S, fog_out, knowledge_out, nullptr, stream);
-    if (rc) return fail(EVG_ERR_HIP, "fog launch failed: %s", hipGetErrorString((hipError_t)rc));
-    return EVG_OK;
+    return launched("fog", launch_fog(h->S, fog_out, knowledge_out, nullptr, stream));
 } catch (...) { return on_exception(); }
 
 int evg_sightings(evg_handle* h, int8_t* sight_out, void* stream) try {
     if (!h || !sight_out) return fail(EVG_ERR_INVALID, "null argument");
     EVG_ON_DEVICE(h);
-    const int rc = launch_fog(h->S, nullptr, nullptr, sight_out, stream);
-    if (rc) return fail(EVG_ERR_HIP, "sightings launch failed: %s", hipGetErrorString((hipError_t)rc));
-    return EVG_OK;
+    return launched("sightings", launch_fog(h->S, nullptr, nullptr, sight_out, stream));
 } catch (...) { return on_exception(); }
 
 int evg_smart_state(evg_handle* h, int player, const void* obs, float* features_out, void* stream) try {
     if (!h || !obs || !features_out || player < 0 || player > 1) return fail(EVG_ERR_INVALID, "bad argument");
     EVG_NEED_ALIGNED16(features_out); EVG_NEED_ALIGNED16(obs);
     EVG_ON_DEVICE(h);
-    const int rc = launch_smart_state(h->S, player, obs, 0, features_out, nullptr, h->cfg.obs_dtype, stream);
-    if (rc) return fail(EVG_ERR_HIP, "smart_state launch failed: %s", hipGetErrorString((hipError_t)rc));
-    return EVG_OK;
+    return launched("smart_state", launch_smart_state(h->S, player, obs, 0, features_out, nullptr, h->cfg.obs_dtype, stream));
 } catch (...) { return on_exception(); }
 
 int evg_smart_state_seat(evg_handle* h, const void* obs_seat, float* features_out, void* stream) try {
     if (!h || !obs_seat || !features_out) return fail(EVG_ERR_INVALID, "bad argument");
     EVG_NEED_ALIGNED16(features_out); EVG_NEED_ALIGNED16(obs_seat);
     EVG_ON_DEVICE(h);
-    const int rc = launch_smart_state(h->S, 0, obs_seat, 1, features_out, nullptr, h->cfg.obs_dtype, stream);
-    if (rc) return fail(EVG_ERR_HIP, "smart_state launch failed: %s", hipGetErrorString((hipError_t)rc));
-    return EVG_OK;
+    return launched("smart_state", launch_smart_state(h->S, 0, obs_seat, 1, features_out, nullptr, h->cfg.obs_dtype, stream));
 } catch (...) { return on_exception(); }
 
 int evg_smart_state_compact(evg_handle* h, int player, const void* obs, float* shared_out, float* swarm_out, void* stream) try {
     if (!h || !obs || !shared_out || !swarm_out || player < -1 || player > 1) return fail(EVG_ERR_INVALID, "bad argument");
-    if ((reinterpret_cast<uintptr_t>(shared_out) & 7u) != 0) return fail(EVG_ERR_INVALID, "shared_out must be 8-byte aligned");
+    if (misaligned8(shared_out)) return fail(EVG_ERR_INVALID, "shared_out must be 8-byte aligned");
     EVG_NEED_ALIGNED16(swarm_out); EVG_NEED_ALIGNED16(obs);
     EVG_ON_DEVICE(h);
-    const int rc = launch_smart_state(h->S, player < 0 ? 0 : player, obs, player < 0 ? 1 : 0, shared_out, swarm_out, h->cfg.obs_dtype, stream);
-    if (rc) return fail(EVG_ERR_HIP, "smart_state launch failed: %s", hipGetErrorString((hipError_t)rc));
-    return EVG_OK;
+    return launched("smart_state", launch_smart_state(h->S, player < 0 ? 0 : player, obs, player < 0 ? 1 : 0, shared_out, swarm_out, h->cfg.obs_dtype, stream));
 } catch (...) { return on_exception(); }
 
 int evg_smart_actions(evg_handle* h, int player, const void* obs, const float* q, int32_t* actions_out, int32_t* directions_out, void* stream) try {
     if (!h || !obs || !q || !actions_out || player < -1 || player > 1) return fail(EVG_ERR_INVALID, "bad argument");
     EVG_NEED_ALIGNED16(obs); EVG_NEED_ALIGNED16(q); EVG_NEED_ALIGNED16(actions_out); EVG_NEED_ALIGNED16(directions_out);
     EVG_ON_DEVICE(h);
-    const int rc = launch_smart_actions(h->S, player < 0 ? 0 : player, obs, player < 0 ? 1 : 0, q, actions_out, directions_out, h->cfg.obs_dtype, stream);
-    if (rc) return fail(EVG_ERR_HIP, "smart_actions launch failed: %s", hipGetErrorString((hipError_t)rc));
-    return EVG_OK;
+    return launched("smart_actions", launch_smart_actions(h->S, player < 0 ? 0 : player, obs, player < 0 ? 1 : 0, q, actions_out, directions_out, h->cfg.obs_dtype, stream));
 } catch (...) { return on_exception(); }
 
 int evg_smart_get_action(evg_handle* h, int seat, int obs_one_seat, const void* obs, const float* q, float epsilon, const float* epsilon_env,
                          int32_t* actions_out, int32_t* directions_out, uint8_t* explored_out, void* stream) try {
     if (!h || !obs || !q || !actions_out || seat < 0 || seat > 1) return fail(EVG_ERR_INVALID, "bad argument");
-    if (!epsilon_env && !(epsilon >= 0.0f && epsilon <= 1.0f)) return fail(EVG_ERR_INVALID, "epsilon %g outside [0, 1]", (double)epsilon);
+    if (const int rc = check_epsilon(epsilon, epsilon_env)) return rc;
     EVG_NEED_ALIGNED16(obs); EVG_NEED_ALIGNED16(q); EVG_NEED_ALIGNED16(actions_out); EVG_NEED_ALIGNED16(directions_out);
     EVG_ON_DEVICE(h);
     const SmartExplore ex{seat, epsilon, epsilon_env, explored_out};
-    const int rc = launch_smart_actions(h->S, seat, obs, obs_one_seat ? 1 : 0, q, actions_out, directions_out, h->cfg.obs_dtype, stream, &ex);
-    if (rc) return fail(EVG_ERR_HIP, "smart_get_action launch failed: %s", hipGetErrorString((hipError_t)rc));
-    return EVG_OK;
+    return launched("smart_get_action", launch_smart_actions(h->S, seat, obs, obs_one_seat ? 1 : 0, q, actions_out, directions_out, h->cfg.obs_dtype, stream, &ex));
 } catch (...) { return on_exception(); }
 
 // ---- the Smart_State replay memory (include/evg.h, evg_replay_*) ----
@@ -868,9 +902,7 @@ static int check_replay(const evg_handle* h, const evg_replay* m) {
 int evg_replay_clear(evg_handle* h, const evg_replay* m, void* stream) try {
     { const int rc = check_replay(h, m); if (rc) return rc; }
     EVG_ON_DEVICE(h);
-    const int rc = launch_replay_clear(h->S, *m, stream);
-    if (rc) return fail(EVG_ERR_HIP, "replay clear launch failed: %s", hipGetErrorString((hipError_t)rc));
-    return EVG_OK;
+    return launched("replay clear", launch_replay_clear(h->S, *m, stream));
 } catch (...) { return on_exception(); }
 
 int evg_replay_record(evg_handle* h, const evg_replay* m, int64_t turn, const float* reward_in, const uint8_t* done_in, const float* custom_in,
@@ -881,17 +913,13 @@ int evg_replay_record(evg_handle* h, const evg_replay* m, int64_t turn, const fl
         return fail(EVG_ERR_INVALID, "replay_record: done_in and %s are required", m->shaping == EVG_SHAPE_CUSTOM ? "custom_in" : "reward_in");
     EVG_NEED_ALIGNED8(reward_in);
     EVG_ON_DEVICE(h);
-    const int rc = launch_replay_record(h->S, *m, (long long)turn, reward_in, done_in, custom_in, stream);
-    if (rc) return fail(EVG_ERR_HIP, "replay record launch failed: %s", hipGetErrorString((hipError_t)rc));
-    return EVG_OK;
+    return launched("replay record", launch_replay_record(h->S, *m, (long long)turn, reward_in, done_in, custom_in, stream));
 } catch (...) { return on_exception(); }
 
 int evg_replay_size(evg_handle* h, const evg_replay* m, void* stream) try {
     { const int rc = check_replay(h, m); if (rc) return rc; }
     EVG_ON_DEVICE(h);
-    const int rc = launch_replay_count(h->S, *m, 0, stream);
-    if (rc) return fail(EVG_ERR_HIP, "replay count launch failed: %s", hipGetErrorString((hipError_t)rc));
-    return EVG_OK;
+    return launched("replay count", launch_replay_count(h->S, *m, 0, stream));
 } catch (...) { return on_exception(); }
 
 static int check_batch_out(int batch, const float* swarm_obs, const int64_t* action, const float* next_state, const float* reward, const uint8_t* not_done,
@@ -913,8 +941,7 @@ int evg_replay_sample(evg_handle* h, const evg_replay* m, int batch, uint64_t se
     int rc = launch_replay_count(h->S, *m, 1, stream);
     if (!rc) rc = launch_replay_draw(h->S, *m, batch, seed, handles, stream);
     if (!rc) rc = launch_replay_gather(h->S, *m, batch, handles, swarm_obs, action, next_state, reward, not_done, stream);
-    if (rc) return fail(EVG_ERR_HIP, "replay sample launch failed: %s", hipGetErrorString((hipError_t)rc));
-    return EVG_OK;
+    return launched("replay sample", rc);
 } catch (...) { return on_exception(); }
 
 int evg_replay_gather(evg_handle* h, const evg_replay* m, int batch, const int32_t* handles, float* swarm_obs, int64_t* action, float* next_state,
@@ -922,9 +949,7 @@ int evg_replay_gather(evg_handle* h, const evg_replay* m, int batch, const int32
     { const int rc = check_replay(h, m); if (rc) return rc; }
     { const int rc = check_batch_out(batch, swarm_obs, action, next_state, reward, not_done, handles); if (rc) return rc; }
     EVG_ON_DEVICE(h);
-    const int rc = launch_replay_gather(h->S, *m, batch, handles, swarm_obs, action, next_state, reward, not_done, stream);
-    if (rc) return fail(EVG_ERR_HIP, "replay gather launch failed: %s", hipGetErrorString((hipError_t)rc));
-    return EVG_OK;
+    return launched("replay gather", launch_replay_gather(h->S, *m, batch, handles, swarm_obs, action, next_state, reward, not_done, stream));
 } catch (...) { return on_exception(); }
 
 // ---- the Smart_State Q network (include/evg.h, evg_smart_qnet) ----
@@ -950,9 +975,7 @@ int evg_smart_qnet(evg_handle* h, const evg_qnet* net, int layout, int64_t rows,
     if (!in0 || !q_out || (layout != EVG_QNET_EXPANDED && !in1)) return fail(EVG_ERR_INVALID, "qnet: in0, q_out and (compact layouts) in1 are required");
     EVG_NEED_ALIGNED16(in0); EVG_NEED_ALIGNED16(in1); EVG_NEED_ALIGNED16(q_out);
     EVG_ON_DEVICE(h);
-    const int rc = launch_smart_qnet(*net, layout, (long long)rows, in0, in1, q_out, h->caps.cus, stream);
-    if (rc) return fail(EVG_ERR_HIP, "qnet launch failed: %s", hipGetErrorString((hipError_t)rc));
-    return EVG_OK;
+    return launched("qnet", launch_smart_qnet(*net, layout, (long long)rows, in0, in1, q_out, h->caps.cus, stream));
 } catch (...) { return on_exception(); }
 
 void evg_move_table(int32_t* table /* [11][5] */) {
@@ -965,9 +988,7 @@ void evg_move_table(int32_t* table /* [11][5] */) {
 int evg_scripted_reset(evg_handle* h, void* stream) try {
     if (!h) return fail(EVG_ERR_INVALID, "null handle");
     EVG_ON_DEVICE(h);
-    const int rc = launch_scripted_reset(h->S, stream);
-    if (rc) return fail(EVG_ERR_HIP, "scripted_reset launch failed: %s", hipGetErrorString((hipError_t)rc));
-    return EVG_OK;
+    return launched("scripted_reset", launch_scripted_reset(h->S, stream));
 } catch (...) { return on_exception(); }
 
 static int rollout_impl(evg_handle* h, int steps, int fused, int policy0, int policy1, int32_t* actions_buf, void* obs_out, float* reward_out,
@@ -999,11 +1020,14 @@ static int rollout_impl(evg_handle* h, int steps, int fused, int policy0, int po
     if (!actions_buf && !fused) return fail(EVG_ERR_INVALID, "rollout: actions_buf is required unless the step kernel produces the orders itself (fused >= 1)");
     EVG_NEED_ALIGNED16(actions_buf); EVG_NEED_ALIGNED16(obs_out); EVG_NEED_ALIGNED8(reward_out); EVG_NEED_ALIGNED8(scores_out);
     EVG_ON_DEVICE(h);
-    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-    hipStream_t s_ = s;
+    hipStream_t s_ = reinterpret_cast<hipStream_t>(stream);
     const bool random_pair = policy0 == EVG_POLICY_RANDOM && policy1 == EVG_POLICY_RANDOM;
     const int gen_mode = random_pair ? 1 : 2;          // what the step kernel draws itself when fused
     if (h->S.mt_key && fused > 1) fused = 1;           // stock-entropy mode: single-turn launches only
+    LaunchIO io(h);
+    io.actions = actions_buf; io.obs = obs_out; io.actions_out = actions_buf;
+    io.reward = reward_out; io.done = done_out; io.winner = winner_out; io.scores = scores_out; io.status = status_out;
+    io.gen_actions = fused ? gen_mode : 0; io.policy0 = policy0; io.policy1 = policy1;
     if (fused >= 2) {
         // Persistent form: one launch plays up to `fused` consecutive turns per wavefront (state stays on chip, outputs are
         // written every turn).  step_kernel_ms then is the launch time divided by the turns it played.
@@ -1014,14 +1038,12 @@ static int rollout_impl(evg_handle* h, int steps, int fused, int policy0, int po
             HIP_TRY(hipEventCreate(&ev));
             h->events.push_back(ev);
         }
-        StepIO io = make_io(h, actions_buf, obs_out, reward_out, done_out, winner_out, scores_out, status_out, 0, gen_mode, policy0, policy1, actions_buf);
         int done_turns = 0;
         for (int l = 0; l < nlaunch; ++l) {
             io.turns = steps - done_turns < per_launch ? steps - done_turns : per_launch;
             if (prepare_only) { (void)graph_of(h, io); done_turns += io.turns; continue; }
             if (step_kernel_ms) HIP_TRY(hipEventRecord(h->events[2 * l], s_));
-            const int rc = launch_rollout(h, io, s_);
-            if (rc) return fail(EVG_ERR_HIP, "step launch failed: %s", hipGetErrorString((hipError_t)rc));
+            if (const int rc = launch_rollout(h, io, s_)) return launched("step", rc);
             if (step_kernel_ms) HIP_TRY(hipEventRecord(h->events[2 * l + 1], s_));
             done_turns += io.turns;
         }
@@ -1039,19 +1061,7 @@ static int rollout_impl(evg_handle* h, int steps, int fused, int policy0, int po
         return EVG_OK;
     }
     if (prepare_only) return EVG_OK;            // single-turn launches are enqueued plainly: nothing to prepare
-    // One launch per turn: the loop is timed as a whole with two events on the stream (an event pair around every launch would
-    // make the queue wait for each bracketed kernel to retire and stretch what it measures): step_kernel_ms is the stream
-    // time per turn -- the step kernel, the gap to the next launch and, when the orders are not drawn by the step kernel
-    // itself (fused == 0), the action kernel(s) of the turn.  The kernel alone is in the rocprofv3 traces under profiles/.
-    while (step_kernel_ms && h->events.size() < 2) {
-        hipEvent_t ev;
-        HIP_TRY(hipEventCreate(&ev));
-        h->events.push_back(ev);
-    }
-    const StepIO io = make_io(h, actions_buf, obs_out, reward_out, done_out, winner_out, scores_out, status_out, 0, fused ? gen_mode : 0, policy0, policy1,
-                              actions_buf);
-    if (step_kernel_ms) HIP_TRY(hipEventRecord(h->events[0], s_));
-    for (int i = 0; i < steps; ++i) {
+    return timed_turns(h, steps, step_kernel_ms, s_, [&] {
         int rc = 0;
         if (fused) {
             // orders are drawn inside the step kernel
@@ -1061,19 +1071,9 @@ static int rollout_impl(evg_handle* h, int steps, int fused, int policy0, int po
             rc = launch_scripted_actions(h->S, policy0, 0, obs_out, actions_buf, h->cfg.obs_dtype, stream);
             if (!rc) rc = launch_scripted_actions(h->S, policy1, 1, obs_out, actions_buf, h->cfg.obs_dtype, stream);
         }
-        if (rc) return fail(EVG_ERR_HIP, "action kernel launch failed: %s", hipGetErrorString((hipError_t)rc));
-        rc = launch_step(h->S, io, h->cfg.obs_dtype, h->caps, stream);
-        if (rc) return fail(EVG_ERR_HIP, "step launch failed: %s", hipGetErrorString((hipError_t)rc));
-    }
-    if (step_kernel_ms) {
-        HIP_TRY(hipEventRecord(h->events[1], s_));
-        HIP_TRY(hipStreamSynchronize(s_));
-        float ms = 0.f;
-        HIP_TRY(hipEventElapsedTime(&ms, h->events[0], h->events[1]));
-        *step_kernel_ms = ms / (float)steps;
-        return check_fault(h);
-    }
-    return EVG_OK;
+        if (rc) return launched("action kernel", rc);
+        return launched("step", launch_step(h->S, io, h->cfg.obs_dtype, h->caps, stream));
+    });
 }
 
 int evg_rollout_vs_policy(evg_handle* h, int steps, int seat, int opponent_policy, int32_t* actions_seat_buf, void* obs_seat_out, float* reward_out,
@@ -1082,34 +1082,20 @@ int evg_rollout_vs_policy(evg_handle* h, int steps, int seat, int opponent_polic
     if (!h) return fail(EVG_ERR_INVALID, "null handle");
     if (steps < 1 || !actions_seat_buf || !obs_seat_out || !reward_out || !done_out)
         return fail(EVG_ERR_INVALID, "rollout_vs_policy: steps >= 1, actions_seat_buf, obs_seat_out, reward_out, done_out required");
-    if (seat < 0 || seat > 1 || opponent_policy < 0 || opponent_policy >= EVG_POLICY_COUNT) return fail(EVG_ERR_INVALID, "seat / opponent_policy out of range");
+    if (const int rc = check_seat_and_opponent(seat, opponent_policy)) return rc;
     EVG_NEED_ALIGNED16(obs_seat_out); EVG_NEED_ALIGNED16(actions_seat_buf); EVG_NEED_ALIGNED8(reward_out); EVG_NEED_ALIGNED8(scores_out);
-    if (h->S.mt_key) return fail(EVG_ERR_INVALID, "evg_rollout_vs_policy: keyed-Philox handles only");
+    if (const int rc = check_keyed_philox(h, "evg_rollout_vs_policy")) return rc;
     EVG_ON_DEVICE(h);
-    hipStream_t s_ = reinterpret_cast<hipStream_t>(stream);
-    while (step_kernel_ms && h->events.size() < 2) {
-        hipEvent_t ev;
-        HIP_TRY(hipEventCreate(&ev));
-        h->events.push_back(ev);
-    }
-    StepIO io = make_io(h, actions_seat_buf, obs_seat_out, reward_out, done_out, winner_out, scores_out, status_out, 0, 2, opponent_policy, opponent_policy,
-                        nullptr);
-    io.seat = seat; io.actions_both = 0;
-    if (step_kernel_ms) HIP_TRY(hipEventRecord(h->events[0], s_));
-    for (int i = 0; i < steps; ++i) {
+    LaunchIO io(h);
+    io.actions = actions_seat_buf; io.obs = obs_seat_out;
+    io.reward = reward_out; io.done = done_out; io.winner = winner_out; io.scores = scores_out; io.status = status_out;
+    io.gen_actions = 2; io.policy0 = io.policy1 = opponent_policy;
+    io.seat = seat;
+    return timed_turns(h, steps, step_kernel_ms, reinterpret_cast<hipStream_t>(stream), [&] {
         int rc = launch_random_actions(h->S, actions_seat_buf, seat, stream);
         if (!rc) rc = launch_step_seat(h->S, io, h->cfg.obs_dtype, h->caps, stream);
-        if (rc) return fail(EVG_ERR_HIP, "launch failed: %s", hipGetErrorString((hipError_t)rc));
-    }
-    if (step_kernel_ms) {
-        HIP_TRY(hipEventRecord(h->events[1], s_));
-        HIP_TRY(hipStreamSynchronize(s_));
-        float ms = 0.f;
-        HIP_TRY(hipEventElapsedTime(&ms, h->events[0], h->events[1]));
-        *step_kernel_ms = ms / (float)steps;
-        return check_fault(h);
-    }
-    return EVG_OK;
+        return launched("", rc);
+    });
 } catch (...) { return on_exception(); }
 
 int evg_seed_stock_entropy(evg_handle* h, const uint32_t* seeds, void* stream) try {
@@ -1123,9 +1109,7 @@ int evg_seed_stock_entropy(evg_handle* h, const uint32_t* seeds, void* stream) t
         HIP_TRY(hipMemcpy(stage, seeds, (size_t)h->S.N * sizeof(uint32_t), hipMemcpyHostToDevice));
         d_seeds = stage;
     }
-    const int rc = launch_mt_seed(h->S, d_seeds, stream);
-    if (rc) return fail(EVG_ERR_HIP, "seed launch failed: %s", hipGetErrorString((hipError_t)rc));
-    return EVG_OK;
+    return launched("seed", launch_mt_seed(h->S, d_seeds, stream));
 } catch (...) { return on_exception(); }
 
 int evg_get_stock_entropy(evg_handle* h, uint32_t* out) try {
@@ -1372,8 +1356,9 @@ EVG_API int evg_debug_read_stamps(evg_handle* h, unsigned long long* out) try {
 int evg_launch_plan(const evg_handle* h, int turns_per_launch, char* buf, int buflen) try {
     if (!h || !buf || buflen < 1 || turns_per_launch < 1) return fail(EVG_ERR_INVALID, "launch_plan: bad argument");
     // the plan of the default rollout: observations written, orders recorded (the pointers are only tested against NULL)
-    StepIO io = make_io(h, nullptr, reinterpret_cast<void*>(16), nullptr, nullptr, nullptr, nullptr, nullptr, 0, 1, 0, 0, reinterpret_cast<int32_t*>(16));
-    io.turns = turns_per_launch;
+    LaunchIO io(h);
+    io.obs = reinterpret_cast<void*>(16); io.actions_out = reinterpret_cast<int32_t*>(16);
+    io.gen_actions = 1; io.turns = turns_per_launch;
     const LaunchPlan p = plan_step(h->S, io, h->cfg.obs_dtype, h->caps);
     std::string s;
     char tmp[320];
@@ -1417,19 +1402,15 @@ int evg_pack_episode_results(evg_handle* h, float* out, void* stream) try {
     if (!h || !out) return fail(EVG_ERR_INVALID, "null argument");
     EVG_NEED_ALIGNED16(out);
     EVG_ON_DEVICE(h);
-    const int rc = launch_pack_results(h->S, out, nullptr, stream);
-    if (rc) return fail(EVG_ERR_HIP, "pack launch failed: %s", hipGetErrorString((hipError_t)rc));
-    return EVG_OK;
+    return launched("pack", launch_pack_results(h->S, out, nullptr, stream));
 } catch (...) { return on_exception(); }
 
 int evg_pack_episode_results_counted(evg_handle* h, float* out, int64_t* counts_out, void* stream) try {
     if (!h || !out || !counts_out) return fail(EVG_ERR_INVALID, "null argument");
     EVG_NEED_ALIGNED16(out);
-    if ((reinterpret_cast<uintptr_t>(counts_out) & 7u) != 0) return fail(EVG_ERR_INVALID, "counts_out must be 8-byte aligned");
+    if (misaligned8(counts_out)) return fail(EVG_ERR_INVALID, "counts_out must be 8-byte aligned");
     EVG_ON_DEVICE(h);
-    const int rc = launch_pack_results(h->S, out, reinterpret_cast<long long*>(counts_out), stream);
-    if (rc) return fail(EVG_ERR_HIP, "pack launch failed: %s", hipGetErrorString((hipError_t)rc));
-    return EVG_OK;
+    return launched("pack", launch_pack_results(h->S, out, reinterpret_cast<long long*>(counts_out), stream));
 } catch (...) { return on_exception(); }
 
 // ---------------------------------------------------------------------------------------------
@@ -1537,7 +1518,7 @@ int evg_gather_returns(evg_handle* h, int root, float* recv_out, void* stream) t
     EVG_ON_DEVICE(h);
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
     const int prc = launch_pack_results(h->S, h->comm_send, nullptr, stream);      // poisoned rows if the handle's fault word is set
-    if (prc) return fail(EVG_ERR_HIP, "pack launch failed: %s", hipGetErrorString((hipError_t)prc));
+    if (prc) return launched("pack", prc);
     // one grouped operation on the caller's stream: every rank sends its rows to the root, the root receives every rank's rows at its offset (global env order)
     RCCL_TRY(R, R->GroupStart());
     ncclResult_t r1 = R->Send(h->comm_send, (size_t)h->S.N * 4, ncclFloat, root, h->comm, s);

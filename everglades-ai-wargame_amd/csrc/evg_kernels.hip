@@ -79,49 +79,68 @@ namespace evg {
 // ---------------------------------------------------------------------------------------------
 // launchers
 // ---------------------------------------------------------------------------------------------
-template <int LPW, bool MULTI>
-static int launch_step_variant(const DevState& S, const StepIO& io, int obs_dtype, hipStream_t s) {
-    const int n = io.env_hi - io.env_lo;
-    const int nsets = (n + LPW / 2 - 1) / (LPW / 2);
-    const dim3 grid((unsigned)nsets), block(WG);
-    const StepArgs args{S, io};
+// obs_dtype (EVG_OBS_*) -> the observation's element type: f is called with a value of that type as a tag (a generic lambda takes it as `auto ot` and
+// names the type decltype(ot)) and its result is returned; -1 for a dtype that does not exist.  The one switch over the observation types in this file.
+template <typename F>
+static int with_obs_type(int obs_dtype, F&& f) {
     switch (obs_dtype) {
-        case EVG_OBS_F32: hipLaunchKernelGGL((evg_step_kernel<float, LPW, MULTI>), grid, block, 0, s, args); break;
-        case EVG_OBS_F64: hipLaunchKernelGGL((evg_step_kernel<double, LPW, MULTI>), grid, block, 0, s, args); break;
-        case EVG_OBS_I16: hipLaunchKernelGGL((evg_step_kernel<int16_t, LPW, MULTI>), grid, block, 0, s, args); break;
+        case EVG_OBS_F32: return f(float{});
+        case EVG_OBS_F64: return f(double{});
+        case EVG_OBS_I16: return f(int16_t{});
         default: return -1;
     }
-    return (int)hipGetLastError();
+}
+
+// The forms of evg_step_kernel that are launched, by name: what each one sets of the kernel's template parameters (step_kernel.inc; its static_asserts
+// guard the combinations).
+struct SingleTurn {                                  // one turn per launch, 32 envs per wavefront, orders read or drawn for both seats
+    static constexpr int lanes = WG;                 // LPW: lanes of a wavefront that hold envs, two per env
+    static constexpr bool multi = false;             // MULTI: the persistent form, io.turns consecutive turns per launch
+    static constexpr bool stock_mt = false;          // MT: the stock-entropy mode's sequential MT19937 draws
+    static constexpr bool chunked = false;           // CHUNKED: workgroups take (set, chunk of turns) units from their XCD's queue
+    static constexpr bool seat = false;              // SEAT: the caller plays one seat, a scripted policy the other; obs is [N][105]
+    static constexpr int waves_per_block = 1;        // WPB: independent wavefronts per workgroup
+    static constexpr bool qdec = false;              // QDEC: orders decoded in the launch from the Q values io.q
+};
+struct Persistent : SingleTurn { static constexpr bool multi = true; };
+struct Chunked : Persistent { static constexpr bool chunked = true; };
+struct StockEntropy : SingleTurn { static constexpr bool stock_mt = true; };
+struct Seat : SingleTurn { static constexpr bool seat = true; };
+struct SeatQ : Seat { static constexpr bool qdec = true; };
+struct TwoSeatQ : SingleTurn { static constexpr bool qdec = true; };
+#ifdef EVG_DIAG
+// diagnostic library, lanes = 32: 16 envs per wavefront + 32 helper lanes, in both launch forms
+template <typename Form> struct HelperLanes : Form { static constexpr int lanes = WG / 2; };
+struct Wg256 : SingleTurn { static constexpr int waves_per_block = 4; };
+#endif
+// (OT, form) -> the kernel, e.g. SeatQ with float32 observations: evg_step_kernel<float, 64, false, false, false, true, 1, true>
+template <typename OT, typename Form>
+constexpr auto step_kernel_of =
+    evg_step_kernel<OT, Form::lanes, Form::multi, Form::stock_mt, Form::chunked, Form::seat, Form::waves_per_block, Form::qdec>;
+
+// One launch of a step-kernel form over envs [io.env_lo, io.env_hi): a wavefront per set of envs -- the chunked form: as many workgroups as the device holds
+// (io.grid_slots), each taking units from its XCD's queue
+template <typename Form>
+static int launch_form(const DevState& S, const StepIO& io, int obs_dtype, hipStream_t s) {
+    constexpr int epw = Form::lanes / 2;
+    const int waves = Form::chunked ? io.grid_slots : (io.env_hi - io.env_lo + epw - 1) / epw;
+    const dim3 grid((unsigned)((waves + Form::waves_per_block - 1) / Form::waves_per_block)), block(WG * Form::waves_per_block);
+    return with_obs_type(obs_dtype, [&](auto ot) {
+        const StepArgs args{S, io};
+        hipLaunchKernelGGL((step_kernel_of<decltype(ot), Form>), grid, block, 0, s, args);
+        return (int)hipGetLastError();
+    });
 }
 
 #ifdef EVG_DIAG
 // round-5 experiment (diagnostic library, lanes = 256): the single-turn form with FOUR independent wavefronts per 256-thread workgroup
-static int launch_step_wg256(const DevState& S, const StepIO& io, int obs_dtype, hipStream_t s) {
-    const int nsets = (io.env_hi - io.env_lo + WG / 2 - 1) / (WG / 2);
-    const dim3 grid((unsigned)((nsets + 3) / 4)), block(4 * WG);
-    const StepArgs args{S, io};
-    switch (obs_dtype) {
-        case EVG_OBS_F32: hipLaunchKernelGGL((evg_step_kernel<float, WG, false, false, false, false, 4>), grid, block, 0, s, args); break;
-        case EVG_OBS_F64: hipLaunchKernelGGL((evg_step_kernel<double, WG, false, false, false, false, 4>), grid, block, 0, s, args); break;
-        case EVG_OBS_I16: hipLaunchKernelGGL((evg_step_kernel<int16_t, WG, false, false, false, false, 4>), grid, block, 0, s, args); break;
-        default: return -1;
-    }
-    return (int)hipGetLastError();
-}
+static int launch_step_wg256(const DevState& S, const StepIO& io, int obs_dtype, hipStream_t s) { return launch_form<Wg256>(S, io, obs_dtype, s); }
 #endif
 
 // the chunked form of the persistent two-lane kernel: as many workgroups as the device holds, each taking units from its XCD's queue
-static int launch_step_chunked(const DevState& S, const StepIO& io, int obs_dtype, hipStream_t s) {
-    const dim3 grid((unsigned)io.grid_slots), block(WG);
-    const StepArgs args{S, io};
-    switch (obs_dtype) {
-        case EVG_OBS_F32: hipLaunchKernelGGL((evg_step_kernel<float, WG, true, false, true>), grid, block, 0, s, args); break;
-        case EVG_OBS_F64: hipLaunchKernelGGL((evg_step_kernel<double, WG, true, false, true>), grid, block, 0, s, args); break;
-        case EVG_OBS_I16: hipLaunchKernelGGL((evg_step_kernel<int16_t, WG, true, false, true>), grid, block, 0, s, args); break;
-        default: return -1;
-    }
-    return (int)hipGetLastError();
-}
+// (this and the one above are functions of their own, defined ahead of everything else that names a kernel, so that the compiler emits the kernels in the
+// order it always did: the device assembly of two builds can then be compared as whole files)
+static int launch_step_chunked(const DevState& S, const StepIO& io, int obs_dtype, hipStream_t s) { return launch_form<Chunked>(S, io, obs_dtype, s); }
 
 // Persistent launches of small and medium batches: the four-lanes-per-env mapping of evg_step4.inc -- 16 envs per wavefront,
 // twice the wavefronts, 2 213 instead of 3 164 vector instructions per wave-turn.  While a SIMD holds few wavefronts, what counts is
@@ -133,21 +152,14 @@ static int launch_step_chunked(const DevState& S, const StepIO& io, int obs_dtyp
 // the two-lane kernel wins.  Same state in HBM, same results (the persistent form of every small-batch test runs this kernel and
 // is compared with the two-lane single-turn form and with the oracle).  The two thresholds are what the DEVICE holds
 // (DeviceCaps::slots4_w2 / slots4_w3 wavefronts of 16 envs), not literals.
-template <typename OT, bool MULTI, int WPE>
-static void launch_step4_t(const DevState& S, const StepIO& io, hipStream_t s) {
-    const StepArgs args{S, io};
-    const dim3 grid((io.env_hi - io.env_lo + 15) / 16), block(WG);
-    hipLaunchKernelGGL((evg_step4_kernel<OT, MULTI, WPE>), grid, block, 0, s, args);
-}
 template <bool MULTI, int WPE>
 static int launch_step4(const DevState& S, const StepIO& io, int obs_dtype, hipStream_t s) {
-    switch (obs_dtype) {
-        case EVG_OBS_F32: launch_step4_t<float, MULTI, WPE>(S, io, s); break;
-        case EVG_OBS_F64: launch_step4_t<double, MULTI, WPE>(S, io, s); break;
-        case EVG_OBS_I16: launch_step4_t<int16_t, MULTI, WPE>(S, io, s); break;
-        default: return -1;
-    }
-    return (int)hipGetLastError();
+    const dim3 grid((io.env_hi - io.env_lo + 15) / 16), block(WG);
+    return with_obs_type(obs_dtype, [&](auto ot) {
+        const StepArgs args{S, io};
+        hipLaunchKernelGGL((evg_step4_kernel<decltype(ot), MULTI, WPE>), grid, block, 0, s, args);
+        return (int)hipGetLastError();
+    });
 }
 
 // What the device holds at once: compute units from hipDeviceProp_t, resident workgroups per CU from the occupancy of the kernels
@@ -156,8 +168,8 @@ static int launch_step4(const DevState& S, const StepIO& io, int obs_dtype, hipS
 template <typename OT>
 static int query_caps_t(DeviceCaps* c) {
     int b2m = 0, b2s = 0, b4w2 = 0, b4w3 = 0;
-    hipError_t e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&b2m, (const void*)evg_step_kernel<OT, WG, true>, WG, 0);
-    if (e == hipSuccess) e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&b2s, (const void*)evg_step_kernel<OT, WG, false>, WG, 0);
+    hipError_t e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&b2m, (const void*)step_kernel_of<OT, Persistent>, WG, 0);
+    if (e == hipSuccess) e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&b2s, (const void*)step_kernel_of<OT, SingleTurn>, WG, 0);
     if (e == hipSuccess) e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&b4w2, (const void*)evg_step4_kernel<OT, true, 2>, WG, 0);
     if (e == hipSuccess) e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&b4w3, (const void*)evg_step4_kernel<OT, true, 3>, WG, 0);
     if (e != hipSuccess) return (int)e;
@@ -178,12 +190,7 @@ int query_device_caps(int device_id, int obs_dtype, DeviceCaps* caps) {
     caps->simds = 4 * caps->cus;
     // MI355X: 256 MiB of Infinity Cache behind 256 CUs; a partition gets its share (evg_config::cache_mib overrides)
     caps->cache_bytes = (256ll << 20) * caps->cus / 256;
-    switch (obs_dtype) {
-        case EVG_OBS_F32: return query_caps_t<float>(caps);
-        case EVG_OBS_F64: return query_caps_t<double>(caps);
-        case EVG_OBS_I16: return query_caps_t<int16_t>(caps);
-        default: return -1;
-    }
+    return with_obs_type(obs_dtype, [&](auto ot) { return query_caps_t<decltype(ot)>(caps); });
 }
 
 // Which kernel plays which envs.  Single-turn launches (evg_step) and the stock-entropy mode: one launch of the two-lane kernel.
@@ -255,33 +262,37 @@ LaunchPlan plan_step(const DevState& S, const StepIO& io, int obs_dtype, const D
 #endif
 }
 
+// The caller's StepIO with the launcher-owned fields set for one plain launch over the whole handle ...
+static StepIO whole_handle_io(const DevState& S, const StepIO& io_in) {
+    StepIO io = io_in;
+    io.env_lo = 0; io.env_hi = S.N; io.flags = 0; io.nsets = 0; io.chunk_turns = 0; io.progress_base = 0; io.grid_slots = 0;
+    return io;
+}
+// ... and that of a single-turn launch: a grid that is resident at once staggers its wavefronts
+static StepIO single_turn_io(const DevState& S, const StepIO& io_in, const DeviceCaps& caps) {
+    StepIO io = whole_handle_io(S, io_in);
+    io.turns = 1;
+    if ((S.N + WG / 2 - 1) / (WG / 2) <= caps.slots2) io.flags |= STEP_F_STAGGER;
+    return io;
+}
+
 int launch_step(const DevState& S, const StepIO& io_in, int obs_dtype, const DeviceCaps& caps, void* stream) {
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-    StepIO io = io_in;
-    const bool multi = io.turns > 1;
-    io.env_lo = 0; io.env_hi = S.N; io.flags = 0; io.nsets = 0; io.chunk_turns = 0; io.progress_base = 0; io.grid_slots = 0;
-    const int grid2 = (S.N + WG / 2 - 1) / (WG / 2);
-    if (!multi && grid2 <= caps.slots2) io.flags |= STEP_F_STAGGER;
+    const bool multi = io_in.turns > 1;
+    StepIO io = multi ? whole_handle_io(S, io_in) : single_turn_io(S, io_in, caps);
     if (S.mt_key) {                       // stock-entropy mode: single-turn launches of the sequential-draw instantiation
         if (multi) return -1;
-        const dim3 grid(grid2), block(WG);
-        const StepArgs args{S, io};
-        switch (obs_dtype) {
-            case EVG_OBS_F32: hipLaunchKernelGGL((evg_step_kernel<float, WG, false, true>), grid, block, 0, s, args); break;
-            case EVG_OBS_F64: hipLaunchKernelGGL((evg_step_kernel<double, WG, false, true>), grid, block, 0, s, args); break;
-            case EVG_OBS_I16: hipLaunchKernelGGL((evg_step_kernel<int16_t, WG, false, true>), grid, block, 0, s, args); break;
-            default: return -1;
-        }
-        return (int)hipGetLastError();
+        return launch_form<StockEntropy>(S, io, obs_dtype, s);
     }
 #ifdef EVG_DIAG
     // the two-lane kernel at any size
-    if (io.lanes_per_wave == 64) return multi ? launch_step_variant<64, true>(S, io, obs_dtype, s) : launch_step_variant<64, false>(S, io, obs_dtype, s);
-    if (io.lanes_per_wave == 256) return multi ? launch_step_variant<64, true>(S, io, obs_dtype, s) : launch_step_wg256(S, io, obs_dtype, s);
+    if (io.lanes_per_wave == 64) return multi ? launch_form<Persistent>(S, io, obs_dtype, s) : launch_form<SingleTurn>(S, io, obs_dtype, s);
+    if (io.lanes_per_wave == 256) return multi ? launch_form<Persistent>(S, io, obs_dtype, s) : launch_step_wg256(S, io, obs_dtype, s);
     if (io.lanes_per_wave == 4) return multi ? launch_step4<true, 4>(S, io, obs_dtype, s) : launch_step4<false, 4>(S, io, obs_dtype, s);
-    if (io.lanes_per_wave == 32) return multi ? launch_step_variant<32, true>(S, io, obs_dtype, s) : launch_step_variant<32, false>(S, io, obs_dtype, s);
+    if (io.lanes_per_wave == 32)
+        return multi ? launch_form<HelperLanes<Persistent>>(S, io, obs_dtype, s) : launch_form<HelperLanes<SingleTurn>>(S, io, obs_dtype, s);
 #endif
-    if (!multi) return launch_step_variant<64, false>(S, io, obs_dtype, s);
+    if (!multi) return launch_form<SingleTurn>(S, io, obs_dtype, s);
     const LaunchPlan plan = plan_step(S, io, obs_dtype, caps);
     for (int i = 0; i < plan.n; ++i) {
         const LaunchPiece& pc = plan.piece[i];
@@ -302,7 +313,7 @@ int launch_step(const DevState& S, const StepIO& io_in, int obs_dtype, const Dev
         if (pc.four_lane_wpe == 2) rc = launch_step4<true, 2>(S, io, obs_dtype, s);
         else if (pc.four_lane_wpe == 3) rc = launch_step4<true, 3>(S, io, obs_dtype, s);
         else if (io.nsets > 0) rc = launch_step_chunked(S, io, obs_dtype, s);
-        else rc = launch_step_variant<64, true>(S, io, obs_dtype, s);
+        else rc = launch_form<Persistent>(S, io, obs_dtype, s);
         if (rc) return rc;
         if (io.nsets > 0) {
             // ... and behind it, on the same stream: every XCD's queue handed out all its units (sets x chunks), or the handle is flagged
@@ -318,50 +329,18 @@ int launch_step(const DevState& S, const StepIO& io_in, int obs_dtype, const Dev
 }
 
 // evg_step_smart_q (self-play): one launch of the two-seat Q form of the single-turn two-lane kernel -- both seats' rows decoded from io.q in the launch
-int launch_step_smart_q(const DevState& S, const StepIO& io_in, int obs_dtype, const DeviceCaps& caps, void* stream) {
-    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-    if (S.mt_key || !io_in.q) return -1;
-    StepIO io = io_in;
-    io.turns = 1; io.env_lo = 0; io.env_hi = S.N; io.flags = 0; io.nsets = 0; io.chunk_turns = 0; io.progress_base = 0; io.grid_slots = 0;
-    const int grid2 = (S.N + WG / 2 - 1) / (WG / 2);
-    if (grid2 <= caps.slots2) io.flags |= STEP_F_STAGGER;
-    const dim3 grid(grid2), block(WG);
-    const StepArgs args{S, io};
-    switch (obs_dtype) {
-        case EVG_OBS_F32: hipLaunchKernelGGL((evg_step_kernel<float, WG, false, false, false, false, 1, true>), grid, block, 0, s, args); break;
-        case EVG_OBS_F64: hipLaunchKernelGGL((evg_step_kernel<double, WG, false, false, false, false, 1, true>), grid, block, 0, s, args); break;
-        case EVG_OBS_I16: hipLaunchKernelGGL((evg_step_kernel<int16_t, WG, false, false, false, false, 1, true>), grid, block, 0, s, args); break;
-        default: return -1;
-    }
-    return (int)hipGetLastError();
+int launch_step_smart_q(const DevState& S, const StepIO& io, int obs_dtype, const DeviceCaps& caps, void* stream) {
+    if (S.mt_key || !io.q) return -1;
+    return launch_form<TwoSeatQ>(S, single_turn_io(S, io, caps), obs_dtype, reinterpret_cast<hipStream_t>(stream));
 }
 
-// evg_step_vs_policy(_smart / _smart_q) / evg_observe_seat: one launch of the one-seat instantiation of the single-turn two-lane kernel (io.q: its Q form)
+// evg_step_vs_policy(_smart / _smart_q) / evg_observe_seat: one launch of the one-seat instantiation of the single-turn two-lane kernel (io.q: its Q form,
+// evg_step_vs_policy_smart_q: an instantiation of its own)
 int launch_step_seat(const DevState& S, const StepIO& io_in, int obs_dtype, const DeviceCaps& caps, void* stream) {
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
     if (S.mt_key) return -1;
-    StepIO io = io_in;
-    io.turns = 1; io.env_lo = 0; io.env_hi = S.N; io.flags = 0; io.nsets = 0; io.chunk_turns = 0; io.progress_base = 0; io.grid_slots = 0;
-    const int grid2 = (S.N + WG / 2 - 1) / (WG / 2);
-    if (grid2 <= caps.slots2) io.flags |= STEP_F_STAGGER;
-    const dim3 grid(grid2), block(WG);
-    const StepArgs args{S, io};
-    if (io.q) {              // the Q form (evg_step_vs_policy_smart_q): an instantiation of its own
-        switch (obs_dtype) {
-            case EVG_OBS_F32: hipLaunchKernelGGL((evg_step_kernel<float, WG, false, false, false, true, 1, true>), grid, block, 0, s, args); break;
-            case EVG_OBS_F64: hipLaunchKernelGGL((evg_step_kernel<double, WG, false, false, false, true, 1, true>), grid, block, 0, s, args); break;
-            case EVG_OBS_I16: hipLaunchKernelGGL((evg_step_kernel<int16_t, WG, false, false, false, true, 1, true>), grid, block, 0, s, args); break;
-            default: return -1;
-        }
-        return (int)hipGetLastError();
-    }
-    switch (obs_dtype) {
-        case EVG_OBS_F32: hipLaunchKernelGGL((evg_step_kernel<float, WG, false, false, false, true>), grid, block, 0, s, args); break;
-        case EVG_OBS_F64: hipLaunchKernelGGL((evg_step_kernel<double, WG, false, false, false, true>), grid, block, 0, s, args); break;
-        case EVG_OBS_I16: hipLaunchKernelGGL((evg_step_kernel<int16_t, WG, false, false, false, true>), grid, block, 0, s, args); break;
-        default: return -1;
-    }
-    return (int)hipGetLastError();
+    const StepIO io = single_turn_io(S, io_in, caps);
+    return io.q ? launch_form<SeatQ>(S, io, obs_dtype, s) : launch_form<Seat>(S, io, obs_dtype, s);
 }
 
 // which XCC ids does this device have?  (evg_create: 1 024 one-wave workgroups report where they ran)
@@ -376,25 +355,20 @@ int launch_xcd_probe(uint32_t* out, void* stream) {
 int launch_reset(const DevState& S, const uint8_t* mask, void* obs, int obs_dtype, void* stream) {
     const dim3 grid((S.N + WG - 1) / WG), block(WG);
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-    switch (obs_dtype) {
-        case EVG_OBS_F32: hipLaunchKernelGGL(evg_reset_kernel<float>, grid, block, 0, s, S, mask, obs); break;
-        case EVG_OBS_F64: hipLaunchKernelGGL(evg_reset_kernel<double>, grid, block, 0, s, S, mask, obs); break;
-        case EVG_OBS_I16: hipLaunchKernelGGL(evg_reset_kernel<int16_t>, grid, block, 0, s, S, mask, obs); break;
-        default: return -1;
-    }
-    return (int)hipGetLastError();
+    return with_obs_type(obs_dtype, [&](auto ot) {
+        hipLaunchKernelGGL(evg_reset_kernel<decltype(ot)>, grid, block, 0, s, S, mask, obs);
+        return (int)hipGetLastError();
+    });
 }
 
 int launch_scripted_actions(const DevState& S, int policy, int player, const void* obs, int32_t* actions, int obs_dtype, void* stream) {
     const dim3 grid((S.N + 255) / 256), block(256);
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-    switch (obs_dtype) {
-        case EVG_OBS_F32: hipLaunchKernelGGL(evg_scripted_actions_kernel<float>, grid, block, 0, s, S, policy, player, (const float*)obs, actions); break;
-        case EVG_OBS_F64: hipLaunchKernelGGL(evg_scripted_actions_kernel<double>, grid, block, 0, s, S, policy, player, (const double*)obs, actions); break;
-        case EVG_OBS_I16: hipLaunchKernelGGL(evg_scripted_actions_kernel<int16_t>, grid, block, 0, s, S, policy, player, (const int16_t*)obs, actions); break;
-        default: return -1;
-    }
-    return (int)hipGetLastError();
+    return with_obs_type(obs_dtype, [&](auto ot) {
+        using OT = decltype(ot);
+        hipLaunchKernelGGL(evg_scripted_actions_kernel<OT>, grid, block, 0, s, S, policy, player, (const OT*)obs, actions);
+        return (int)hipGetLastError();
+    });
 }
 
 int launch_mt_seed(const DevState& S, const uint32_t* seeds_dev, void* stream) {
@@ -407,23 +381,18 @@ int launch_scripted_reset(const DevState& S, void* stream) {
     return (int)hipGetLastError();
 }
 
-template <typename OT>
-static void launch_smart_state_t(int n, const dim3 grid, hipStream_t s, int player, int seat_only, const void* obs, float* out, float* out_swarm) {
-    if (out_swarm) hipLaunchKernelGGL((evg_smart_state_kernel<OT, true>), grid, dim3(256), 0, s, n, player, seat_only, (const OT*)obs, out, out_swarm);
-    else hipLaunchKernelGGL((evg_smart_state_kernel<OT, false>), grid, dim3(256), 0, s, n, player, seat_only, (const OT*)obs, out, out_swarm);
-}
 // out_swarm non-NULL: compact form, out = shared [N][34]
 int launch_smart_state(const DevState& S, int player, const void* obs, int seat_only, float* out, float* out_swarm, int obs_dtype, void* stream) {
     const int blocks = (S.N + 3) / 4;                       // one wavefront per env and pass; 8 blocks per CU resident, further envs in passes
     const dim3 grid((unsigned)(blocks < 2048 ? blocks : 2048));
+    const dim3 block(256);
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-    switch (obs_dtype) {
-        case EVG_OBS_F32: launch_smart_state_t<float>(S.N, grid, s, player, seat_only, obs, out, out_swarm); break;
-        case EVG_OBS_F64: launch_smart_state_t<double>(S.N, grid, s, player, seat_only, obs, out, out_swarm); break;
-        case EVG_OBS_I16: launch_smart_state_t<int16_t>(S.N, grid, s, player, seat_only, obs, out, out_swarm); break;
-        default: return -1;
-    }
-    return (int)hipGetLastError();
+    return with_obs_type(obs_dtype, [&](auto ot) {
+        using OT = decltype(ot);
+        if (out_swarm) hipLaunchKernelGGL((evg_smart_state_kernel<OT, true>), grid, block, 0, s, S.N, player, seat_only, (const OT*)obs, out, out_swarm);
+        else hipLaunchKernelGGL((evg_smart_state_kernel<OT, false>), grid, block, 0, s, S.N, player, seat_only, (const OT*)obs, out, out_swarm);
+        return (int)hipGetLastError();
+    });
 }
 
 // network output -> orders: one DPP row (16 lanes) per env
@@ -437,17 +406,12 @@ int launch_smart_actions(const DevState& S, int player, const void* obs, int sea
     int2* d = reinterpret_cast<int2*>(directions);
     ExploreArgs X{};
     if (ex) X = ExploreArgs{S.seed_lo, S.seed_hi, S.env_id_base, S.episode, ex->seat, ex->eps, ex->eps_env, ex->explored};
-#define EVG_LAUNCH_SMART(OT)                                                                                                                     \
-    if (ex) hipLaunchKernelGGL((evg_smart_actions_kernel<OT, true>), grid, block, 0, s, S.N, player, seat_only, (const OT*)obs, q, a, d, X);      \
-    else hipLaunchKernelGGL((evg_smart_actions_kernel<OT, false>), grid, block, 0, s, S.N, player, seat_only, (const OT*)obs, q, a, d, X)
-    switch (obs_dtype) {
-        case EVG_OBS_F32: EVG_LAUNCH_SMART(float); break;
-        case EVG_OBS_F64: EVG_LAUNCH_SMART(double); break;
-        case EVG_OBS_I16: EVG_LAUNCH_SMART(int16_t); break;
-        default: return -1;
-    }
-#undef EVG_LAUNCH_SMART
-    return (int)hipGetLastError();
+    return with_obs_type(obs_dtype, [&](auto ot) {
+        using OT = decltype(ot);
+        if (ex) hipLaunchKernelGGL((evg_smart_actions_kernel<OT, true>), grid, block, 0, s, S.N, player, seat_only, (const OT*)obs, q, a, d, X);
+        else hipLaunchKernelGGL((evg_smart_actions_kernel<OT, false>), grid, block, 0, s, S.N, player, seat_only, (const OT*)obs, q, a, d, X);
+        return (int)hipGetLastError();
+    });
 }
 
 int launch_fog(const DevState& S, uint8_t* fog, uint8_t* know, int8_t* sight, void* stream) {

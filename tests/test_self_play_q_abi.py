@@ -1,6 +1,7 @@
 """CPU tests (no GPU needed) of evg_step_smart_q, the self-play turn from both seats' Q values: the prototype include/evg.h declares and the ctypes binding
 agree, and the kernel instantiation it launches -- the two-seat Q form of the plain single-turn kernel -- fits that kernel's budget (no scratch, no spills,
 the same LDS, 2 waves per SIMD)."""
+import importlib.util
 import os
 import re
 import subprocess
@@ -10,6 +11,14 @@ import pytest
 from conftest import ROOT
 
 CSRC = os.path.join(ROOT, "everglades-ai-wargame_amd", "csrc")
+
+
+def _step_kernel_symbol(form, obs_dtype):
+    """tools/_prof.py knows the symbol of a step-kernel form"""
+    spec = importlib.util.spec_from_file_location("evg_prof", os.path.join(ROOT, "tools", "_prof.py"))
+    prof = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(prof)
+    return prof.step_kernel_symbol(form, obs_dtype)
 
 
 def _prototype_arity(header, name):
@@ -44,9 +53,9 @@ def _resource_usage():
 @pytest.mark.skipif(not os.path.exists("/opt/rocm/bin/hipcc"), reason="needs hipcc")
 def test_two_seat_q_form_fits_the_plain_kernel_budget():
     usage = _resource_usage()
-    for ot in "fds":                                             # float, double, int16 observations
-        plain = usage["_ZN3evg15evg_step_kernelI%sLi64ELb0ELb0ELb0ELb0ELi1ELb0EEEvNS_8StepArgsE" % ot]
-        qform = usage["_ZN3evg15evg_step_kernelI%sLi64ELb0ELb0ELb0ELb0ELi1ELb1EEEvNS_8StepArgsE" % ot]
+    for ot in ("float32", "float64", "int16"):
+        plain = usage[_step_kernel_symbol("single_turn", ot)]
+        qform = usage[_step_kernel_symbol("two_seat_q", ot)]
         assert qform["ScratchSize [bytes/lane]"] == "0" and qform["VGPRs Spill"] == "0" and qform["SGPRs Spill"] == "0", (ot, qform)
         assert int(qform["LDS Size [bytes/block]"]) <= 20480 and qform["LDS Size [bytes/block]"] == plain["LDS Size [bytes/block]"], (ot, qform)
         assert qform["Occupancy [waves/SIMD]"] == plain["Occupancy [waves/SIMD]"] == "2", (ot, qform, plain)

@@ -1,5 +1,6 @@
 """CPU tests (no GPU needed) of evg_step_vs_policy_smart_q, the Smart_State learner's turn from its Q values: the prototype include/evg.h declares and the
 ctypes binding agree, and the kernel instantiation it launches fits the budget of the one-seat kernel it is a form of (no scratch, the same LDS and occupancy)."""
+import importlib.util
 import os
 import re
 import subprocess
@@ -9,6 +10,14 @@ import pytest
 from conftest import ROOT
 
 CSRC = os.path.join(ROOT, "everglades-ai-wargame_amd", "csrc")
+
+
+def _step_kernel_symbol(form, obs_dtype):
+    """tools/_prof.py knows the symbol of a step-kernel form"""
+    spec = importlib.util.spec_from_file_location("evg_prof", os.path.join(ROOT, "tools", "_prof.py"))
+    prof = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(prof)
+    return prof.step_kernel_symbol(form, obs_dtype)
 
 
 def _prototype_arity(header, name):
@@ -40,9 +49,9 @@ def _resource_usage():
 @pytest.mark.skipif(not os.path.exists("/opt/rocm/bin/hipcc"), reason="needs hipcc")
 def test_q_form_of_the_seat_kernel_fits_the_seat_kernel_budget():
     usage = _resource_usage()
-    for ot in "fds":                                             # float, double, int16 observations
-        seat = usage["_ZN3evg15evg_step_kernelI%sLi64ELb0ELb0ELb0ELb1ELi1ELb0EEEvNS_8StepArgsE" % ot]
-        qform = usage["_ZN3evg15evg_step_kernelI%sLi64ELb0ELb0ELb0ELb1ELi1ELb1EEEvNS_8StepArgsE" % ot]
+    for ot in ("float32", "float64", "int16"):
+        seat = usage[_step_kernel_symbol("seat", ot)]
+        qform = usage[_step_kernel_symbol("seat_q", ot)]
         assert qform["ScratchSize [bytes/lane]"] == "0" and qform["VGPRs Spill"] == "0" and qform["SGPRs Spill"] == "0", (ot, qform)
         assert int(qform["LDS Size [bytes/block]"]) <= 20480 and qform["LDS Size [bytes/block]"] == seat["LDS Size [bytes/block]"], (ot, qform)
         assert qform["Occupancy [waves/SIMD]"] == seat["Occupancy [waves/SIMD]"] == "2", (ot, qform, seat)

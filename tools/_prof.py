@@ -46,6 +46,23 @@ def step_kernel(name, form):
     return "evg_step4_kernel<%s, %s" % (dtype, multi) in name
 
 
+# The step-kernel forms the launchers name (csrc/evg_kernels.hip: SingleTurn, Persistent, ...): what each sets of evg_step_kernel's template parameters
+# <OT, LPW, MULTI, MT, CHUNKED, SEAT, WPB, QDEC>, after the observation type
+STEP_FORMS = {"single_turn": (64, 0, 0, 0, 0, 1, 0), "persistent": (64, 1, 0, 0, 0, 1, 0), "chunked": (64, 1, 0, 1, 0, 1, 0),
+              "stock_entropy": (64, 0, 1, 0, 0, 1, 0), "seat": (64, 0, 0, 0, 1, 1, 0), "seat_q": (64, 0, 0, 0, 1, 1, 1),
+              "two_seat_q": (64, 0, 0, 0, 0, 1, 1),
+              # diagnostic libraries only
+              "helper_lanes": (32, 0, 0, 0, 0, 1, 0), "helper_lanes_persistent": (32, 1, 0, 0, 0, 1, 0), "wg256": (64, 0, 0, 0, 0, 4, 0)}
+OBS_MANGLED = {"float32": "f", "float64": "d", "int16": "s"}
+
+
+def step_kernel_symbol(form, obs_dtype="float32"):
+    """the mangled symbol of a step-kernel form (a key of STEP_FORMS) for an observation type: what nm, the device assembly and the compiler's
+    resource-usage remarks call it"""
+    lpw, multi, mt, chunked, seat, wpb, qdec = STEP_FORMS[form]
+    return "_ZN3evg15evg_step_kernelI%sLi%dELb%dELb%dELb%dELb%dELi%dELb%dEEEvNS_8StepArgsE" % (OBS_MANGLED[obs_dtype], lpw, multi, mt, chunked, seat, wpb, qdec)
+
+
 def counter_rows(directory, form):
     """{counter: [value per dispatch, in dispatch order]} and the matching [duration ns] of the step kernel of `form`."""
     f = glob.glob(os.path.join(directory, "*", "*_counter_collection.csv"))[0]

@@ -14,7 +14,9 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join(ROOT, "everglades-ai-wargame_amd", "csrc")
 NAMES = ["tables+state load", "orders", "combat0 snapshot", "combat1 worklist", "combatA draws", "combatB apply", "movement",
          "aggregates+capture", "rewards+stats+reset", "obs build", "state store", "obs write-out", "reset fill"]
-KERNEL = "_ZN3evg15evg_step_kernelIfLi64ELb1ELb0ELb0ELb0ELi1EEEvNS_8StepArgsE"
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import _prof  # noqa: E402
+KERNEL = _prof.step_kernel_symbol("persistent", "float32")
 KINDS = ("valu", "salu", "lds", "vmem", "branch", "waitcnt")
 
 
