@@ -29,6 +29,7 @@ POLICY_ALIASES = {"random_actions": 0, "random_actions_2": 0, "swarm_agent": 3, 
 EXPORTS = ["evg_default_tables", "evg_create", "evg_destroy", "evg_reset", "evg_step", "evg_observe", "evg_step_vs_policy", "evg_step_vs_policy_smart",
            "evg_step_vs_policy_smart_q", "evg_step_smart_q", "evg_replay_clear", "evg_replay_record", "evg_replay_size", "evg_replay_sample",
            "evg_replay_gather", "evg_smart_qnet",
+           "evg_league_clear", "evg_league_assign", "evg_league_importance", "evg_step_vs_league", "evg_step_vs_league_q",
            "evg_observe_seat",
            "evg_random_actions_seat", "evg_smart_state_seat", "evg_smart_state_compact", "evg_check_fault", "evg_rollout_vs_policy", "evg_fog_of_war",
            "evg_sightings", "evg_smart_state", "evg_smart_actions", "evg_smart_get_action", "evg_move_table", "evg_random_actions", "evg_rollout_random", "evg_rollout_policies",
@@ -110,6 +111,17 @@ class EvgQnet(C.Structure):
     ]
 
 
+class EvgLeague(C.Structure):
+    """evg_league of include/evg.h: the descriptor of an opponent league (device pointers the caller owns)."""
+    _fields_ = [
+        ("num_members", C.c_int32), ("members", C.c_int32 * 16), ("seat", C.c_int32), ("resample", C.c_int32),
+        ("weights", C.c_void_p), ("assign", C.c_void_p), ("objects", C.c_void_p), ("counts", C.c_void_p), ("ctl", C.c_void_p),
+    ]
+
+
+LEAGUE_MAX_MEMBERS = 16
+LEAGUE_S_BAD_WEIGHTS, LEAGUE_S_BAD_ASSIGN = 1, 2              # EVG_LEAGUE_S_*
+ERR_ARG = -1          # EVG_ERR_ARG (= EVG_ERR_INVALID): a bad argument, e.g. a league descriptor out of range
 QNET_COMPACT, QNET_COMPACT_SEATS, QNET_EXPANDED = 0, 1, 2     # EVG_QNET_*
 QNET_MAX_HIDDEN, QNET_MAX_ROWS = 64, 1 << 30
 
@@ -198,6 +210,12 @@ def load(path=None):
     L.evg_replay_sample.argtypes = [vp, rp, C.c_int, C.c_uint64, vp, vp, vp, vp, vp, vp, vp]
     L.evg_replay_gather.argtypes = [vp, rp, C.c_int, vp, vp, vp, vp, vp, vp, vp]
     L.evg_smart_qnet.argtypes = [vp, C.POINTER(EvgQnet), C.c_int, C.c_int64, vp, vp, vp, vp]
+    lp = C.POINTER(EvgLeague)
+    L.evg_league_clear.argtypes = [vp, lp, vp]
+    L.evg_league_assign.argtypes = [vp, lp, vp, vp]
+    L.evg_league_importance.argtypes = [vp, lp, vp, vp]
+    L.evg_step_vs_league.argtypes = [vp, vp, C.c_int, lp, vp, vp, vp, vp, vp, vp, vp, vp, vp]
+    L.evg_step_vs_league_q.argtypes = [vp, vp, C.c_float, vp, lp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]
     L.evg_random_actions_seat.argtypes = [vp, C.c_int, vp, vp]
     L.evg_smart_state_seat.argtypes = [vp, vp, vp, vp]
     L.evg_smart_state_compact.argtypes = [vp, C.c_int, vp, vp, vp, vp]

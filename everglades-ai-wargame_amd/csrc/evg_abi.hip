@@ -194,16 +194,18 @@ static int check_fault(evg_handle* h, uint32_t* word_out = nullptr) {
 // The key of the graph cache: every field of StepIO that the caller owns (the launcher-owned ones -- env_lo, env_hi, flags, nsets, chunk_turns, grid_slots,
 // progress_base -- are set by launch_step inside the captured plan).  A new field of StepIO changes its size: visit same_launch, then the number.
 #ifdef EVG_DIAG
-static_assert(sizeof(StepIO) == 200, "StepIO changed (diagnostic layout): visit same_launch");
+static_assert(sizeof(StepIO) == 256, "StepIO changed (diagnostic layout): visit same_launch");
 #else
-static_assert(sizeof(StepIO) == 184, "StepIO changed: visit same_launch");
+static_assert(sizeof(StepIO) == 240, "StepIO changed: visit same_launch");
 #endif
 static bool same_launch(const StepIO& a, const StepIO& b) {
     bool same = a.actions == b.actions && a.obs == b.obs && a.reward == b.reward && a.done == b.done && a.winner == b.winner && a.scores == b.scores &&
                 a.status == b.status && a.observe_only == b.observe_only && a.gen_actions == b.gen_actions && a.policy0 == b.policy0 &&
                 a.policy1 == b.policy1 && a.actions_out == b.actions_out && a.turns == b.turns && a.seat == b.seat && a.actions_both == b.actions_both &&
                 a.feat_shared == b.feat_shared && a.feat_swarm == b.feat_swarm && a.q == b.q && a.eps == b.eps && a.eps1 == b.eps1 &&
-                a.eps_env == b.eps_env && a.q_actions == b.q_actions && a.q_directions == b.q_directions && a.q_explored == b.q_explored;
+                a.eps_env == b.eps_env && a.q_actions == b.q_actions && a.q_directions == b.q_directions && a.q_explored == b.q_explored &&
+                a.lg_weights == b.lg_weights && a.lg_assign == b.lg_assign && a.lg_objects == b.lg_objects && a.lg_counts == b.lg_counts &&
+                a.lg_ctl == b.lg_ctl && a.lg_members == b.lg_members && a.lg_num == b.lg_num && a.lg_resample == b.lg_resample;
 #ifdef EVG_DIAG
     same = same && a.lanes_per_wave == b.lanes_per_wave && a.ablate == b.ablate && a.stamps == b.stamps;
 #endif
@@ -976,6 +978,90 @@ int evg_smart_qnet(evg_handle* h, const evg_qnet* net, int layout, int64_t rows,
     EVG_NEED_ALIGNED16(in0); EVG_NEED_ALIGNED16(in1); EVG_NEED_ALIGNED16(q_out);
     EVG_ON_DEVICE(h);
     return launched("qnet", launch_smart_qnet(*net, layout, (long long)rows, in0, in1, q_out, h->caps.cus, stream));
+} catch (...) { return on_exception(); }
+
+// ---- the opponent league (include/evg.h, evg_league) ----
+static int check_league(const evg_handle* h, const evg_league* lg) {
+    if (!h || !lg) return fail(EVG_ERR_ARG, "null handle or league descriptor");
+    if (lg->num_members < 1 || lg->num_members > EVG_LEAGUE_MAX_MEMBERS)
+        return fail(EVG_ERR_ARG, "league: num_members must lie in 1..%d (got %d)", EVG_LEAGUE_MAX_MEMBERS, lg->num_members);
+    for (int m = 0; m < lg->num_members; ++m)
+        if (lg->members[m] < 0 || lg->members[m] >= EVG_POLICY_COUNT) return fail(EVG_ERR_ARG, "league: member %d is no EVG_POLICY_* id (got %d)", m, lg->members[m]);
+    if (lg->seat < 0 || lg->seat > 1) return fail(EVG_ERR_ARG, "league: seat must be 0 or 1 (got %d)", lg->seat);
+    if (lg->resample != 0 && lg->resample != 1) return fail(EVG_ERR_ARG, "league: resample must be 0 or 1 (got %d)", lg->resample);
+    if (!lg->weights || !lg->assign || !lg->objects || !lg->counts || !lg->ctl) return fail(EVG_ERR_ARG, "league: every buffer of the descriptor is required");
+    EVG_NEED_ALIGNED8(lg->weights); EVG_NEED_ALIGNED8(lg->counts); EVG_NEED_ALIGNED8(lg->ctl);
+    if (reinterpret_cast<uintptr_t>(lg->objects) % 4) return fail(EVG_ERR_ARG, "league: objects must be 4-byte aligned");
+    if (const int rc = check_keyed_philox(h, "evg_league", " (the stock-entropy mode has no fused bots)")) return rc;
+    return EVG_OK;
+}
+static void league_io(StepIO& io, const evg_league* lg) {
+    io.gen_actions = 2; io.policy0 = io.policy1 = lg->members[0];
+    io.seat = lg->seat;
+    io.lg_weights = lg->weights; io.lg_assign = lg->assign; io.lg_objects = lg->objects; io.lg_counts = lg->counts; io.lg_ctl = lg->ctl;
+    io.lg_members = 0;
+    for (int m = 0; m < lg->num_members; ++m) io.lg_members |= (uint64_t)lg->members[m] << (4 * m);
+    io.lg_num = lg->num_members; io.lg_resample = lg->resample;
+}
+
+int evg_league_clear(evg_handle* h, const evg_league* lg, void* stream) try {
+    { const int rc = check_league(h, lg); if (rc) return rc; }
+    EVG_ON_DEVICE(h);
+    return launched("league clear", launch_league_clear(h->S, *lg, stream));
+} catch (...) { return on_exception(); }
+
+int evg_league_assign(evg_handle* h, const evg_league* lg, const uint8_t* mask, void* stream) try {
+    { const int rc = check_league(h, lg); if (rc) return rc; }
+    if (!lg->resample) return EVG_OK;
+    EVG_ON_DEVICE(h);
+    return launched("league assign", launch_league_assign(h->S, *lg, mask, stream));
+} catch (...) { return on_exception(); }
+
+int evg_league_importance(evg_handle* h, const evg_league* lg, double* weights_out, void* stream) try {
+    { const int rc = check_league(h, lg); if (rc) return rc; }
+    if (!weights_out) return fail(EVG_ERR_ARG, "league_importance: weights_out is required");
+    EVG_NEED_ALIGNED8(weights_out);
+    EVG_ON_DEVICE(h);
+    return launched("league importance", launch_league_importance(*lg, weights_out, stream));
+} catch (...) { return on_exception(); }
+
+int evg_step_vs_league(evg_handle* h, const int32_t* actions, int actions_both_seats, const evg_league* lg, void* obs_seat_out, float* shared_out,
+                       float* swarm_out, float* reward_out, uint8_t* done_out, int8_t* winner_out, int32_t* scores_out, uint8_t* status_out, void* stream) try {
+    if (!h) return fail(EVG_ERR_INVALID, "null handle");
+    if (!actions || !obs_seat_out || !reward_out || !done_out) return fail(EVG_ERR_INVALID, "actions, obs_seat_out, reward_out and done_out are required");
+    { const int rc = check_league(h, lg); if (rc) return rc; }
+    if (const int rc = check_feature_pair(shared_out, swarm_out)) return rc;
+    EVG_NEED_ALIGNED16(obs_seat_out); EVG_NEED_ALIGNED16(actions); EVG_NEED_ALIGNED8(reward_out); EVG_NEED_ALIGNED8(scores_out);
+    EVG_NEED_ALIGNED16(shared_out); EVG_NEED_ALIGNED16(swarm_out);
+    EVG_ON_DEVICE(h);
+    LaunchIO io(h);
+    io.actions = actions; io.obs = obs_seat_out;
+    io.reward = reward_out; io.done = done_out; io.winner = winner_out; io.scores = scores_out; io.status = status_out;
+    league_io(io, lg);
+    io.actions_both = actions_both_seats ? 1 : 0;
+    io.feat_shared = shared_out; io.feat_swarm = swarm_out;
+    return launched("step", launch_step_league(h->S, io, h->cfg.obs_dtype, h->caps, stream));
+} catch (...) { return on_exception(); }
+
+int evg_step_vs_league_q(evg_handle* h, const float* q, float epsilon, const float* epsilon_env, const evg_league* lg, void* obs_seat_out, float* shared_out,
+                         float* swarm_out, int32_t* actions_out, int32_t* directions_out, uint8_t* explored_out, float* reward_out, uint8_t* done_out,
+                         int8_t* winner_out, int32_t* scores_out, uint8_t* status_out, void* stream) try {
+    if (!h) return fail(EVG_ERR_INVALID, "null handle");
+    if (!q || !obs_seat_out || !reward_out || !done_out) return fail(EVG_ERR_INVALID, "q, obs_seat_out, reward_out and done_out are required");
+    { const int rc = check_league(h, lg); if (rc) return rc; }
+    if (const int rc = check_epsilon(epsilon, epsilon_env)) return rc;
+    if (const int rc = check_feature_pair(shared_out, swarm_out)) return rc;
+    EVG_NEED_ALIGNED16(q); EVG_NEED_ALIGNED16(obs_seat_out); EVG_NEED_ALIGNED16(shared_out); EVG_NEED_ALIGNED16(swarm_out);
+    EVG_NEED_ALIGNED16(actions_out); EVG_NEED_ALIGNED16(directions_out); EVG_NEED_ALIGNED8(reward_out); EVG_NEED_ALIGNED8(scores_out);
+    EVG_ON_DEVICE(h);
+    LaunchIO io(h);
+    io.obs = obs_seat_out;
+    io.reward = reward_out; io.done = done_out; io.winner = winner_out; io.scores = scores_out; io.status = status_out;
+    league_io(io, lg);
+    io.feat_shared = shared_out; io.feat_swarm = swarm_out;
+    io.q = q; io.eps = epsilon; io.eps_env = epsilon_env;
+    io.q_actions = actions_out; io.q_directions = directions_out; io.q_explored = explored_out;
+    return launched("step", launch_step_league(h->S, io, h->cfg.obs_dtype, h->caps, stream));
 } catch (...) { return on_exception(); }
 
 void evg_move_table(int32_t* table /* [11][5] */) {

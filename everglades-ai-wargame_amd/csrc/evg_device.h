@@ -158,6 +158,16 @@ struct StepIO {
     int32_t*  q_actions;         // [N][7][2] or NULL: the rows played (evg_smart_get_action's actions_out); two-seat Q form: [N][2][7][2]
     int32_t*  q_directions;      // [N][7][2] or NULL: {swarm, direction}; two-seat Q form: [N][2][7][2]
     uint8_t*  q_explored;        // [N] or NULL: 1 where the random branch ran; two-seat Q form: [N][2]
+    // LEAGUE forms of the SEAT instantiation (evg_step_vs_league / evg_step_vs_league_q; include/evg.h, evg_league): the bot of seat 1 - seat is a per-env
+    // quantity.  All zero / NULL for every other entry point (LaunchIO), which launch kernels that never read them
+    const double* lg_weights;    // [lg_num] caller-owned, read only when an episode starts (resample)
+    uint8_t*  lg_assign;         // [N] the member every env plays in its current episode
+    uint32_t* lg_objects;        // [lg_num][3][N] the members' agent objects that are not live (words: cycle, swarm, dfs)
+    unsigned long long* lg_counts;   // [lg_num][4] games, wins, ties, losses per member, seen from the caller's seat
+    unsigned long long* lg_ctl;  // [2] {status bits EVG_LEAGUE_S_*, reserved}
+    uint64_t  lg_members;        // nibble m = EVG_POLICY_* id of member m
+    int32_t   lg_num;            // members, 1..16
+    int32_t   lg_resample;       // 1: a new episode draws its member (league_choice); 0: lg_assign is the caller's and never changes
 #ifdef EVG_DIAG                  // diagnostic libraries only (libevg_diag.so, libevg_stamps.so)
     int32_t   lanes_per_wave;    // 64: 32 envs per wavefront; 32: 16 envs per wavefront + 32 helper lanes
     uint32_t  ablate;            // bit0 orders, bit1 combat, bit2 movement, bit4 obs write-out, bit5 state store
@@ -194,6 +204,11 @@ LaunchPlan plan_step(const DevState& S, const StepIO& io, int obs_dtype, const D
 long long rollout_bytes_per_env(const StepIO& io, int obs_dtype);
 int launch_step(const DevState& S, const StepIO& io, int obs_dtype, const DeviceCaps& caps, void* stream);
 int launch_step_seat(const DevState& S, const StepIO& io, int obs_dtype, const DeviceCaps& caps, void* stream);
+int launch_step_league(const DevState& S, const StepIO& io, int obs_dtype, const DeviceCaps& caps, void* stream);
+// the opponent league's side kernels (league_kernels.inc); `lg` is validated by the caller (evg_abi.hip)
+int launch_league_clear(const DevState& S, const evg_league& lg, void* stream);
+int launch_league_assign(const DevState& S, const evg_league& lg, const uint8_t* mask, void* stream);
+int launch_league_importance(const evg_league& lg, double* weights_out, void* stream);
 int launch_step_smart_q(const DevState& S, const StepIO& io, int obs_dtype, const DeviceCaps& caps, void* stream);
 int launch_reset(const DevState& S, const uint8_t* mask, void* obs, int obs_dtype, void* stream);
 int launch_random_actions(const DevState& S, int32_t* actions, int seat /* -1: both, [N][2][7][2]; 0 / 1: that seat only, [N][7][2] */, void* stream);

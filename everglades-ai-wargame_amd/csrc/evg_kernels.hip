@@ -64,6 +64,7 @@ namespace evg {
 #include "step_common.inc"      // LDS layout of a wavefront's envs, phase fence, sorting network, small device helpers
 #include "step_rules.inc"       // the rules of a turn, written once for both lane mappings (pure register functions)
 #include "step_agents.inc"      // the scripted opponents (one device function over a view)
+#include "league_choice.inc"    // the opponent league's member draw and object swap (the step kernel's league forms and league_kernels.inc)
 #include "smart_decode.inc"     // the Smart_State agent's decode of its Q values (the standalone kernel and the step kernel's Q form)
 #include "step_kernel.inc"      // evg_step_kernel: skeleton + the phases of a turn (step_orders / step_combat / step_move_capture / step_outputs .inc)
 
@@ -75,6 +76,7 @@ namespace evg {
 #include "side_kernels.inc"     // pack, chunk-queue check, reset, seeding, action generators, fog planes, Smart_State features
 #include "replay_kernels.inc"   // the Smart_State learner's n-step replay memory: record, count, draw, gather
 #include "qnet_kernels.inc"     // the Smart_State Q network's forward pass (inference) on v_mfma_f32_16x16x4_f32
+#include "league_kernels.inc"   // the opponent league: clear, assign after an explicit reset, importance weights
 
 // ---------------------------------------------------------------------------------------------
 // launchers
@@ -101,6 +103,7 @@ struct SingleTurn {                                  // one turn per launch, 32 
     static constexpr bool seat = false;              // SEAT: the caller plays one seat, a scripted policy the other; obs is [N][105]
     static constexpr int waves_per_block = 1;        // WPB: independent wavefronts per workgroup
     static constexpr bool qdec = false;              // QDEC: orders decoded in the launch from the Q values io.q
+    static constexpr bool league = false;            // LEAGUE: the scripted policy of the other seat is a per-env member of an opponent league (io.lg_*)
 };
 struct Persistent : SingleTurn { static constexpr bool multi = true; };
 struct Chunked : Persistent { static constexpr bool chunked = true; };
@@ -108,15 +111,18 @@ struct StockEntropy : SingleTurn { static constexpr bool stock_mt = true; };
 struct Seat : SingleTurn { static constexpr bool seat = true; };
 struct SeatQ : Seat { static constexpr bool qdec = true; };
 struct TwoSeatQ : SingleTurn { static constexpr bool qdec = true; };
+struct SeatLeague : Seat { static constexpr bool league = true; };
+struct SeatQLeague : SeatQ { static constexpr bool league = true; };
 #ifdef EVG_DIAG
 // diagnostic library, lanes = 32: 16 envs per wavefront + 32 helper lanes, in both launch forms
 template <typename Form> struct HelperLanes : Form { static constexpr int lanes = WG / 2; };
 struct Wg256 : SingleTurn { static constexpr int waves_per_block = 4; };
 #endif
-// (OT, form) -> the kernel, e.g. SeatQ with float32 observations: evg_step_kernel<float, 64, false, false, false, true, 1, true>
+// (OT, form) -> the kernel, e.g. SeatQ with float32 observations: evg_step_kernel<float, 64, false, false, false, true, 1, true, false>
 template <typename OT, typename Form>
 constexpr auto step_kernel_of =
-    evg_step_kernel<OT, Form::lanes, Form::multi, Form::stock_mt, Form::chunked, Form::seat, Form::waves_per_block, Form::qdec>;
+    evg_step_kernel<OT, Form::lanes, Form::multi, Form::stock_mt, Form::chunked, Form::seat, Form::waves_per_block, Form::qdec,
+                    Form::league>;
 
 // One launch of a step-kernel form over envs [io.env_lo, io.env_hi): a wavefront per set of envs -- the chunked form: as many workgroups as the device holds
 // (io.grid_slots), each taking units from its XCD's queue
@@ -343,6 +349,14 @@ int launch_step_seat(const DevState& S, const StepIO& io_in, int obs_dtype, cons
     return io.q ? launch_form<SeatQ>(S, io, obs_dtype, s) : launch_form<Seat>(S, io, obs_dtype, s);
 }
 
+// evg_step_vs_league(_q): the league forms of the one-seat kernel (io.q: with the Q decode)
+int launch_step_league(const DevState& S, const StepIO& io_in, int obs_dtype, const DeviceCaps& caps, void* stream) {
+    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+    if (S.mt_key || !io_in.lg_assign) return -1;
+    const StepIO io = single_turn_io(S, io_in, caps);
+    return io.q ? launch_form<SeatQLeague>(S, io, obs_dtype, s) : launch_form<SeatLeague>(S, io, obs_dtype, s);
+}
+
 // which XCC ids does this device have?  (evg_create: 1 024 one-wave workgroups report where they ran)
 __global__ void __launch_bounds__(WG) evg_xcd_probe_kernel(uint32_t* out) {
     if (threadIdx.x == 0) out[blockIdx.x] = __builtin_amdgcn_s_getreg(63508) & 15u;      // HW_REG_XCC_ID
@@ -426,6 +440,26 @@ int launch_pack_results(const DevState& S, float* out, long long* counts, void* 
         if (me != hipSuccess) return (int)me;
     }
     hipLaunchKernelGGL(evg_pack_results_kernel, dim3((S.N + 255) / 256), dim3(256), 0, s, S, reinterpret_cast<float4*>(out), counts);
+    return (int)hipGetLastError();
+}
+
+static LeagueArgs league_args(const evg_league& lg) {
+    return LeagueArgs{lg.weights, lg.assign, lg.objects, lg.counts, lg.ctl, lg.num_members, lg.seat, lg.resample ? 1 : 0};
+}
+int launch_league_clear(const DevState& S, const evg_league& lg, void* stream) {
+    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+    hipError_t me = hipMemsetAsync(lg.counts, 0, (size_t)lg.num_members * 4 * sizeof(unsigned long long), s);
+    if (me == hipSuccess) me = hipMemsetAsync(lg.ctl, 0, 2 * sizeof(unsigned long long), s);
+    if (me != hipSuccess) return (int)me;
+    hipLaunchKernelGGL(evg_league_clear_kernel, dim3((S.N + 255) / 256), dim3(256), 0, s, S, league_args(lg));
+    return (int)hipGetLastError();
+}
+int launch_league_assign(const DevState& S, const evg_league& lg, const uint8_t* mask, void* stream) {
+    hipLaunchKernelGGL(evg_league_assign_kernel, dim3((S.N + 255) / 256), dim3(256), 0, reinterpret_cast<hipStream_t>(stream), S, league_args(lg), mask);
+    return (int)hipGetLastError();
+}
+int launch_league_importance(const evg_league& lg, double* weights_out, void* stream) {
+    hipLaunchKernelGGL(evg_league_importance_kernel, dim3(1), dim3(WG), 0, reinterpret_cast<hipStream_t>(stream), league_args(lg), weights_out);
     return (int)hipGetLastError();
 }
 

@@ -34,13 +34,19 @@ typedef const StepArgs __attribute__((address_space(4))) * step_args_ptr;
 // QDEC without SEAT (evg_step_smart_q): the Q form of the plain single-turn kernel -- self-play, a DQNAgent on each seat: both seats' rows are decoded in the
 // prologue, one seat per pass through the same LDS (the two seats' Q values, 15 360 B per wave, do not fit the union at once), and both players' features are
 // written after the observation write-out.
-template <typename OT, int LPW, bool MULTI, bool MT = false, bool CHUNKED = false, bool SEAT = false, int WPB = 1, bool QDEC = false>
+// LEAGUE (evg_step_vs_league / evg_step_vs_league_q): SEAT or SEAT + QDEC with the bot as a PER-ENV quantity -- the opponent league of include/evg.h
+// (evg_league).  The league lane's policy id is a per-lane value: assign[e], loaded in the prologue's round trip next to the agent words, picks it from the
+// member ids in the kernel arguments, and agent_rows -- a chain over a runtime `policy` -- runs with it (lanes of a wave that play different bots take their
+// branches one after the other).  The step that ends an episode tallies it per member; with auto_reset the reset branch also draws the member of the next
+// episode (league_choice) and, when it changes, swaps the agent object with the member's slot of the league store.
+template <typename OT, int LPW, bool MULTI, bool MT = false, bool CHUNKED = false, bool SEAT = false, int WPB = 1, bool QDEC = false, bool LEAGUE = false>
 __global__ void __launch_bounds__(WG * WPB) __attribute__((amdgpu_waves_per_eu(2, 2))) evg_step_kernel(StepArgs) {
     static_assert(!MT || (!MULTI && LPW == WG), "the stock-entropy mode exists in the single-turn, 32-envs-per-wave form only");
     static_assert(!CHUNKED || (MULTI && LPW == WG && !MT), "the chunked form is an instantiation of the persistent two-lane kernel");
     static_assert(!SEAT || (!MULTI && !MT && LPW == WG), "the one-seat form is an instantiation of the single-turn two-lane kernel");
     static_assert(WPB == 1 || (!MULTI && !MT && !CHUNKED && !SEAT && LPW == WG), "several wavefronts per workgroup: the plain single-turn two-lane form only");
     static_assert(!QDEC || (!MULTI && !MT && LPW == WG && WPB == 1), "the Q form is an instantiation of the single-turn two-lane kernel (one seat or two)");
+    static_assert(!LEAGUE || SEAT, "the league forms are instantiations of the one-seat kernel (with or without the Q decode)");
     step_args_ptr A = (step_args_ptr)__builtin_amdgcn_kernarg_segment_ptr();
     constexpr int EPW = LPW / 2;                        // envs per wavefront
     constexpr int DP_CAP = CombatLds<LPW>::DP_CAP;
@@ -153,6 +159,9 @@ __global__ void __launch_bounds__(WG * WPB) __attribute__((amdgpu_waves_per_eu(2
     uint32_t ag_cycle = 0, ag_swarm = 0, ag_dfs = 0;
     const size_t ai = (size_t)P * N + e;
     if (io.gen_actions == 2) { ag_cycle = S.agent_cycle[ai]; ag_swarm = S.agent_swarm[ai]; ag_dfs = S.agent_dfs[ai]; }
+    // league forms: the member this env plays (both lanes of the pair hold it: player 0's lane tallies, the league seat's lane plays and swaps)
+    [[maybe_unused]] uint32_t lg_raw = 0u;
+    if constexpr (LEAGUE) lg_raw = io.lg_assign[e];
     // caller-supplied orders (evg_step): this player's 7 rows are part of the same round trip
     int2 act_in[NA];
 #pragma unroll
@@ -271,6 +280,17 @@ __global__ void __launch_bounds__(WG * WPB) __attribute__((amdgpu_waves_per_eu(2
     // makes the compiler put s_waitcnt vmcnt(0) in front of its first use inside the loop, where it would wait for the previous
     // turn's observation stores on every turn.
     asm volatile("" :: "v"(episode), "v"(ep_ret), "v"(ag_cycle), "v"(ag_swarm), "v"(ag_dfs));
+    [[maybe_unused]] int lg_m = 0, lg_pol = 0;
+    if constexpr (LEAGUE) {
+        asm volatile("" :: "v"(lg_raw));
+        // a value >= M (only a caller's own write can be one) plays member 0 and is reported
+        if (lg_raw >= (uint32_t)io.lg_num) {
+            if (valid && P != io.seat) atomicOr(io.lg_ctl, (unsigned long long)EVG_LEAGUE_S_BAD_ASSIGN);
+            lg_raw = 0u;
+        }
+        lg_m = (int)lg_raw;
+        lg_pol = (int)((io.lg_members >> (4u * lg_raw)) & 15ull);
+    }
     if constexpr (QDEC) {
         // ---- Q form: the caller's 7 rows from its network output (DQNAgent.get_action, agents/Smart_State/DQNAgent.py:130-198), the whole wavefront at
         // once -- one DPP row (16 lanes) per env, lane = swarm, four envs per pass -- with the rules of evg_smart_actions_kernel (smart_decode.inc).  The

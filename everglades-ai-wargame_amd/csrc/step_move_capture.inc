@@ -2,7 +2,8 @@
 // rewards / done / winner, episode bookkeeping and auto-reset.
 // reads:  L.G, L.NW, L.tab, st[3], play, valid, turn, status, episode, ep_ret, spd_n / ctl_n / cst_n, max_turns
 // writes: gw[12] (this lane's group words after the turn), st[3], cntv[12], L.NW (capture), L.u.A (units listed per node), score[2], status,
-//         turn / episode (reset), ep_ret, do_reset, the per-env outputs (reward, done, winner, scores, status) and the episode results
+//         turn / episode (reset), ep_ret, do_reset, the per-env outputs (reward, done, winner, scores, status) and the episode results;
+//         league forms: io.lg_counts (tally), and in the reset branch io.lg_assign, io.lg_objects, the agent words (member redraw and object swap)
     // ---------------- movement of this lane's groups (server.py:656-706), branch-free
     uint32_t gw[12];
 #pragma unroll
@@ -129,6 +130,26 @@
                 if (n1) atomicAdd(&S.totals[2], (unsigned long long)n1);
                 if (nf - n0 - n1) atomicAdd(&S.totals[3], (unsigned long long)(nf - n0 - n1));
             }
+            if constexpr (LEAGUE) {
+                // ... and per league member, seen from the caller's seat (include/evg.h, evg_league COUNTERS: the winner code is the script's decision
+                // from the final rewards), in the same pattern: one pass per member that finished a game in this wave, lane 0 adds the pass's counts
+                uint64_t rest = mf;
+                while (rest) {
+                    const int m = __builtin_amdgcn_readlane(lg_m, __ffsll((unsigned long long)rest) - 1);
+                    const bool mine = fin && lg_m == m;
+                    const uint64_t mm = __ballot(mine);
+                    // (EVG_WINNER_P0 / P1 are the seats' numbers)
+                    const int ng = __popcll(mm), nw = __popcll(__ballot(mine && winner == io.seat)), nt = __popcll(__ballot(mine && winner == EVG_WINNER_TIE));
+                    if (lane == 0) {
+                        unsigned long long* const c = io.lg_counts + 4 * m;
+                        atomicAdd(&c[0], (unsigned long long)ng);
+                        if (nw) atomicAdd(&c[1], (unsigned long long)nw);
+                        if (nt) atomicAdd(&c[2], (unsigned long long)nt);
+                        if (ng - nw - nt) atomicAdd(&c[3], (unsigned long long)(ng - nw - nt));
+                    }
+                    rest &= ~mm;
+                }
+            }
         }
     }
     if (do_reset) {
@@ -148,6 +169,26 @@
 #pragma unroll
         for (int n = 0; n < 12; ++n) L.u.A[n][lane] = 0;
         L.u.A[gw[0] & G_LOC_M][lane] = (uint32_t)NU << 16;
+        if constexpr (LEAGUE) {
+            // the league seat's lane: the member of the episode that starts (the draw is keyed by the NEW episode index), and when it is another one, the
+            // object swap -- the live words to the old member's slot, the new member's become the live ones.  The weights (at most 16 doubles) and the
+            // swap's loads and stores are touched only here, once per episode and env
+            if (P != io.seat && io.lg_resample) {
+                bool bad = false;
+                // (the seed is made opaque here: the draw's key schedule is then computed in this branch, once per episode, instead of being shared with
+                // the prologue's Philox blocks and kept in scalar registers across the whole turn, which spilled six of them in the Q form)
+                uint32_t lg_seed_lo = S.seed_lo, lg_seed_hi = S.seed_hi;
+                asm volatile("" : "+s"(lg_seed_lo), "+s"(lg_seed_hi));
+                const int m_new = league_choice(lg_seed_lo, lg_seed_hi, S.env_id_base + (uint32_t)e, episode, P, io.lg_weights, io.lg_num, lg_m, bad);
+                if (bad) atomicOr(io.lg_ctl, (unsigned long long)EVG_LEAGUE_S_BAD_WEIGHTS);
+                if (m_new != lg_m) {
+                    league_swap(io.lg_objects, N, (size_t)e, lg_m, m_new, ag_cycle, ag_swarm, ag_dfs);
+                    const size_t ai_ = (size_t)P * N + e;
+                    S.agent_cycle[ai_] = ag_cycle; S.agent_swarm[ai_] = ag_swarm; S.agent_dfs[ai_] = ag_dfs;
+                    io.lg_assign[e] = (uint8_t)m_new;
+                }
+            }
+        }
     }
     WAVE_SYNC();        // node words final; everybody is done adding to A
     PHASE(9);

@@ -23,7 +23,9 @@
             asm volatile("" : "+s"(pol0), "+s"(pol1));
             const AgentTabs atabs{L.tab.nib[11], L.tab.nib[12], L.tab.nib[13], T};
             const bool bot_lane = !SEAT || P != io.seat;        // one-seat form: the caller's lane has no agent (its object is neither consulted nor stored)
-            agent_rows(P ? pol1 : pol0, view, atabs, S.seed_lo, S.seed_hi, S.env_id_base + (uint32_t)e, episode, P, true, status == 0 && bot_lane,
+            int pol = P ? pol1 : pol0;
+            if constexpr (LEAGUE) pol = lg_pol;                 // a per-lane value: the env's member (the caller's lane is not a bot lane)
+            agent_rows(pol, view, atabs, S.seed_lo, S.seed_hi, S.env_id_base + (uint32_t)e, episode, P, true, status == 0 && bot_lane,
                        &ag_cycle, &ag_swarm, &ag_dfs, act);
             if constexpr (SEAT) {
 #pragma unroll

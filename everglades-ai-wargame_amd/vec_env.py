@@ -11,6 +11,7 @@ import os
 import numpy as np
 
 from . import _lib
+from .league import OpponentLeague
 from .tables import default_tables, tables_from_json
 
 
@@ -208,13 +209,14 @@ class EvergladesVecEnv(object):
         """One turn of the loop the reference's training and evaluation scripts run (evaluate.py:143-152;
         agents/Smart_State/training_scripts/dqn_smart_state_training.py:114-122): the caller plays `seat` with `actions` -- int32
         [N, 7, 2], or a [N, 2, 7, 2] tensor whose rows [:, seat] are used --, the on-device scripted bot `policy` (a name from
-        _lib.POLICY_NAMES or an EVG_POLICY_* id) plays the other seat, evaluated INSIDE the step kernel from the on-chip state
+        _lib.POLICY_NAMES, an EVG_POLICY_* id, or an OpponentLeague: a bot per env, evg_step_vs_league) plays the other seat, evaluated INSIDE the step kernel from the on-chip state
         (evg_step_vs_policy: one launch, no opponent observations or orders through HBM).  Returns (obs_seat [N, 105] -- the caller's
         seat only --, reward [N, 2], done [N], info) like step(); bit-identical to scripted_actions(policy, 1 - seat) + step().
         features=(shared [N, 34], swarm [N, 12, 13]) float32 tensors: the launch ALSO writes the Smart_State features of the new observation into them
         (evg_step_vs_policy_smart: what smart_state_compact(-1, obs_seat, shared, swarm) would compute afterwards, without that kernel)."""
         torch = _torch()
-        pid = self.POLICIES[policy] if isinstance(policy, str) else int(policy)
+        league = policy if isinstance(policy, OpponentLeague) else None
+        pid = None if league is not None else (self.POLICIES[policy] if isinstance(policy, str) else int(policy))
         a = actions
         if not (type(a) is torch.Tensor and a.dtype is self._int32 and a.device == self.device and a.is_contiguous()):
             a = torch.as_tensor(actions, device=self.device)
@@ -227,7 +229,15 @@ class EvergladesVecEnv(object):
             raise ValueError("actions must have shape [N, 7, 2] (the caller's seat) or [N, 2, 7, 2], got %s" % (tuple(a.shape),))
         obs = self._seat_buffers() if out is None else self._user(out, (self.num_envs, _lib.OBS_LEN), self.obs_dtype, "out")
         p = self._p
-        if features is not None:
+        if league is not None:               # a per-env bot (evg_step_vs_league): the caller's seat is the league's
+            shared = swarm = None
+            if features is not None:
+                shared, swarm = features
+                self._user(shared, (self.num_envs, 34), torch.float32, "features[0] (shared)")
+                self._user(swarm, (self.num_envs, _lib.NUM_GROUPS, 13), torch.float32, "features[1] (swarm)")
+            rc = self.L.evg_step_vs_league(self._h, C.c_void_p(a.data_ptr()), both, self._league(league, seat), C.c_void_p(obs.data_ptr()), self._ptr(shared),
+                                           self._ptr(swarm), p["reward"], p["done"], p["winner"], p["scores"], p["status"], self._stream())
+        elif features is not None:
             shared, swarm = features
             self._user(shared, (self.num_envs, 34), torch.float32, "features[0] (shared)")
             self._user(swarm, (self.num_envs, _lib.NUM_GROUPS, 13), torch.float32, "features[1] (swarm)")
@@ -243,13 +253,14 @@ class EvergladesVecEnv(object):
 
     def step_vs_q(self, policy, q, epsilon, seat=0, features=None, directions=None, explored=None, actions_out=None, out=None):
         """The Smart_State learner's turn from its Q values, in ONE launch (evg_step_vs_policy_smart_q): DQNAgent.get_action for `seat` -- the epsilon
-        coin, then get_random_actions or get_best_actions, as smart_get_action() -- then step_vs(policy) with those rows.  `q` float32 [N, 12, 5]: the
+        coin, then get_random_actions or get_best_actions, as smart_get_action() -- then step_vs(policy) with those rows (`policy` as in step_vs(), an OpponentLeague included).  `q` float32 [N, 12, 5]: the
         network's output; `epsilon` a float in [0, 1] or a float32 tensor [N].  Returns (obs_seat [N, 105], reward [N, 2], done [N], info) like step_vs();
         bit-identical to smart_get_action(q, epsilon, seat, obs=<the previous seat observation>) + step_vs(policy, rows, seat).  features=(shared [N, 34],
         swarm [N, 12, 13]) as in step_vs() (shared 16-byte aligned); `directions` / `actions_out` int32 [N, 7, 2] receive {swarm, direction} / the rows
         played, `explored` uint8 [N] 1 where the random branch ran.  No host synchronisation and no allocation per call: it can sit inside a captured loop."""
         torch = _torch()
-        pid = self.POLICIES[policy] if isinstance(policy, str) else int(policy)
+        league = policy if isinstance(policy, OpponentLeague) else None
+        pid = None if league is not None else (self.POLICIES[policy] if isinstance(policy, str) else int(policy))
         N = self.num_envs
         self._user(q, (N, _lib.NUM_GROUPS, 5), torch.float32, "q")
         obs = self._seat_buffers() if out is None else self._user(out, (N, _lib.OBS_LEN), self.obs_dtype, "out")
@@ -269,6 +280,14 @@ class EvergladesVecEnv(object):
             eps_env = self._user(epsilon, (N,), torch.float32, "epsilon")
             epsilon = 0.0
         p = self._p
+        if league is not None:               # a per-env bot (evg_step_vs_league_q): the caller's seat is the league's
+            rc = self.L.evg_step_vs_league_q(self._h, C.c_void_p(q.data_ptr()), float(epsilon), self._ptr(eps_env), self._league(league, seat),
+                                             C.c_void_p(obs.data_ptr()), self._ptr(shared), self._ptr(swarm), self._ptr(actions_out),
+                                             self._ptr(directions), self._ptr(explored), p["reward"], p["done"], p["winner"], p["scores"], p["status"],
+                                             self._stream())
+            if rc:
+                self._check(rc)
+            return obs, self.reward, self.done, self._info
         rc = self.L.evg_step_vs_policy_smart_q(self._h, int(seat), C.c_void_p(q.data_ptr()), float(epsilon), self._ptr(eps_env), pid,
                                                C.c_void_p(obs.data_ptr()), self._ptr(shared), self._ptr(swarm), self._ptr(actions_out),
                                                self._ptr(directions), self._ptr(explored), p["reward"], p["done"], p["winner"], p["scores"], p["status"],
@@ -317,6 +336,20 @@ class EvergladesVecEnv(object):
         if rc:
             self._check(rc)
         return obs, self.reward, self.done, self._info
+
+    def _league(self, league, seat):
+        """the descriptor of `league` for a step of this env (the caller's seat is the league's; an explicit other `seat` is a mistake)"""
+        if league.env is not self:
+            raise ValueError("the league belongs to another env")
+        if int(seat) not in (0, league.seat):
+            raise ValueError("seat=%d, but the league was created for seat %d" % (int(seat), league.seat))
+        return league._ref
+
+    def opponent_league(self, members, weights=None, seat=0, resample=True):
+        """A per-env scripted opponent for step_vs() / step_vs_q(), redrawn by weight each episode (everglades_amd.OpponentLeague; evg_league): the
+        curriculum of dqn_smart_state_cycled_training_with_importance.py, or -- resample=False and a caller-written `assign` -- evaluate_all.py's
+        one-learner-against-every-bot."""
+        return OpponentLeague(self, members, weights=weights, seat=seat, resample=resample)
 
     def rollout_vs(self, steps, policy, seat=0, time_kernel=False):
         """`steps` turns of the learner-seat loop driven from native code (evg_rollout_vs_policy): per turn the on-device random_actions

@@ -39,7 +39,9 @@ extern "C" {
 #define EVG_ABI_VERSION 7
 /* 7: evg_step_vs_policy_smart_q (the Smart_State learner's turn from its Q values: DQNAgent.get_action decoded inside the learner-seat step launch);
  *    evg_step_smart_q (the self-play turn: both seats' Q values decoded inside one step launch; an added function, no layout changed);
- *    evg_smart_qnet with its descriptor evg_qnet: the Smart_State Q network's forward pass in one launch (added, no layout changed) */
+ *    evg_smart_qnet with its descriptor evg_qnet: the Smart_State Q network's forward pass in one launch (added, no layout changed);
+ *    the opponent league: evg_league_clear / evg_league_assign / evg_league_importance / evg_step_vs_league / evg_step_vs_league_q with their descriptor
+ *    evg_league -- added, no layout changed */
 /* 6: evg_smart_get_action (DQNAgent.get_action with epsilon > 0), evg_step_vs_policy_smart (the learner-seat turn that also writes the Smart_State
  *    features), evg_get_run_state / evg_set_run_state (agent objects, returns, win counters: checkpoint / resume); reward / score buffers need 8-byte
  *    alignment only (5 asked 16 of every buffer)
@@ -67,6 +69,7 @@ extern "C" {
 typedef enum evg_status {
     EVG_OK = 0,
     EVG_ERR_INVALID = -1,      /* bad argument / table out of the supported domain */
+    EVG_ERR_ARG = EVG_ERR_INVALID,   /* the same status under the name the league entry points' contract uses */
     EVG_ERR_NO_DEVICE = -2,    /* no usable HIP device (there is no CPU path)        */
     EVG_ERR_HIP = -3,          /* a HIP runtime call failed                         */
     EVG_ERR_ALLOC = -4,
@@ -645,6 +648,73 @@ typedef struct evg_qnet {
     const float* b3[2];
 } evg_qnet;
 EVG_API int evg_smart_qnet(evg_handle* h, const evg_qnet* net, int layout, int64_t rows, const float* in0, const float* in1, float* q_out, void* stream);
+
+/* ---- The opponent league: a per-env scripted opponent, redrawn by weight each episode -----------------------------------------------------------------
+ * agents/Smart_State/training_scripts/dqn_smart_state_cycled_training_with_importance.py: every episode the opponent is
+ * random.choices(opposing_agents, opposing_agent_weights)[0] from 15 scripted bots (:68-160, :210), games and wins are tallied per bot (:281-285) and every
+ * 50 episodes the weights move towards the bots the learner loses to (updateAgentWeights, :166-173, :319-322); evaluate_all.py is the same need with a
+ * fixed opponent per game.  Added under ABI 7: new functions and one new descriptor struct; nothing that existed changed.
+ *
+ * A league is an ordered list of M members, 1 <= M <= EVG_LEAGUE_MAX_MEMBERS, each an EVG_POLICY_* id.  Ids may repeat (the script lists random_actions
+ * and random_actions_2, same_commands and same_commands_2): repeated ids are distinct members with their own agent objects and counters.  The league plays
+ * seat 1 - seat against the caller's `seat`.  Storage is caller-owned device memory (everglades_amd.OpponentLeague allocates it):
+ *   weights  const double [M]      read when an episode starts, so the caller may rewrite it on the stream at any time (evg_league_importance does)
+ *   assign   uint8 [N]             the member env e plays in its current episode
+ *   objects  uint32 [M][3][N]      member m's agent object of env e: the three words the handle keeps per (env, player) -- {cycle word, SwarmAgent's
+ *                                  attack list, dfs_attack's call counter} at objects[(m * 3 + w) * N + e].  The CURRENT member's object is the handle's
+ *                                  live one of the league seat (evg_get_run_state `agents`[e][1 - seat]); its slot here is stale until the member changes
+ *   counts   uint64 [M][4]         {games, wins, ties, losses} against member m, seen from the caller's seat
+ *   ctl      uint64 [2]            {status bits EVG_LEAGUE_S_* (sticky until evg_league_clear), reserved}
+ * ASSIGNMENT.  resample = 1: the member of env e for its episode k is random.choices(range(M), weights) restated on a keyed draw (DESIGN.md section 4,
+ * domain 5): cum[j] = weights[0] + ... + weights[j] in float64, left to right; total = cum[M - 1] + 0.0; x = u * total with u = (double)w / 4294967296.0,
+ * w = word .x of the Philox block (domain 5, block 0, turn 0, node 0, player 1 - seat, group 0, episode k, global env id); member = the number of
+ * j < M - 1 with cum[j] <= x, i.e. bisect(cum, x, 0, M - 1).  A 32-bit uniform stands in for random.random()'s 53 bits, as the coin of
+ * random_actions_delay does.  If total is not finite or <= 0 (the reference raises ValueError) the env keeps its member and EVG_LEAGUE_S_BAD_WEIGHTS is set.
+ * resample = 0: the caller writes assign (e.g. arange(N) % M) and it is never redrawn; a value >= M plays member 0 and sets EVG_LEAGUE_S_BAD_ASSIGN.
+ * AGENT OBJECTS live across episodes like the script's 15 bot instances (:68-160).  When an env's member changes at an episode boundary the live words go
+ * to the old member's slot and the new member's are loaded: a member playing for the first time still has first_turn set, a returning one continues
+ * where it stopped.
+ * COUNTERS.  The step that ends an episode (with or without auto_reset) increments counts[m][0] and one of counts[m][1..3].  The script decides from the
+ * step's final rewards (:282-289: reward[0] > reward[1] win, == tie, else loss); the step's winner code is the same decision -- a finished game's rewards
+ * are (1, -1), (0, 1) or (0, 0) for EVG_WINNER_P0 / P1 / TIE (everglades_env.py:37-61), so reward[seat] > reward[1 - seat] <=> winner == seat and
+ * equality <=> EVG_WINNER_TIE, for either seat -- and is what the kernel uses.
+ * WHERE.  With auto_reset the tally, the draw for episode k + 1 and the object swap run inside the step launch that ends episode k: the next launch finds
+ * everything in place.  Without auto_reset the tally still happens in the step; draw and swap are evg_league_assign, enqueued after evg_reset(mask). */
+#define EVG_LEAGUE_MAX_MEMBERS 16
+enum { EVG_LEAGUE_S_BAD_WEIGHTS = 1, EVG_LEAGUE_S_BAD_ASSIGN = 2 };
+typedef struct evg_league {
+    int32_t num_members;                        /* M, 1..16                                             */
+    int32_t members[EVG_LEAGUE_MAX_MEMBERS];    /* EVG_POLICY_* of member m (entries >= M are ignored)  */
+    int32_t seat;                               /* the CALLER's seat, 0 or 1; the league plays 1 - seat */
+    int32_t resample;                           /* 0 / 1                                                */
+    const double* weights;
+    uint8_t* assign;
+    uint32_t* objects;
+    unsigned long long* counts;
+    unsigned long long* ctl;
+} evg_league;
+/* Every member object of every env becomes fresh (the values evg_scripted_reset writes), the handle's live objects of the league seat too; counters and
+ * status are zeroed; with resample every env's member is drawn for its current episode index (resample = 0: assign is left to the caller). */
+EVG_API int evg_league_clear(evg_handle* h, const evg_league* lg, void* stream);
+/* Draw and swap for the envs of mask (device uint8 [N]; NULL = all), for their current episode: call it after an explicit evg_reset(mask).  A no-op for
+ * resample = 0. */
+EVG_API int evg_league_assign(evg_handle* h, const evg_league* lg, const uint8_t* mask, void* stream);
+/* updateAgentWeights (:166-173) on the device: weights_out[m] = 1.0 where games == 0, else 1.0 - wins / games + 0.05, in float64 (both counters converted
+ * exactly, one division, one subtraction, one addition -- Python's order).  weights_out: device double [M]; it may be lg->weights. */
+EVG_API int evg_league_importance(evg_handle* h, const evg_league* lg, double* weights_out, void* stream);
+/* evg_step_vs_policy_smart / evg_step_vs_policy_smart_q against the league: the argument lists of those two with `lg` where opponent_policy stands and
+ * the caller's seat taken from lg->seat; shared_out / swarm_out are optional in both (both NULL or both set, both 16-byte aligned: the fused feature store
+ * writes float4).  Argument checks, error codes, alignment rules and launch as in the seat family; a descriptor whose num_members, member ids or seat are out
+ * of range (or that lacks a buffer) is refused with EVG_ERR_ARG before anything is enqueued.  Results -- every output, assign, and afterwards the handle's
+ * state and run state, objects and counts -- are bit for bit those of playing every env against its member with the entry points above, the member's
+ * object moved in and out of the handle at the episode boundaries.  Keyed-Philox handles only. */
+EVG_API int evg_step_vs_league(evg_handle* h, const int32_t* actions, int actions_both_seats, const evg_league* lg, void* obs_seat_out,
+                               float* shared_out, float* swarm_out, float* reward_out, uint8_t* done_out, int8_t* winner_out, int32_t* scores_out,
+                               uint8_t* status_out, void* stream);
+EVG_API int evg_step_vs_league_q(evg_handle* h, const float* q, float epsilon, const float* epsilon_env, const evg_league* lg,
+                                 void* obs_seat_out, float* shared_out, float* swarm_out,
+                                 int32_t* actions_out, int32_t* directions_out, uint8_t* explored_out,
+                                 float* reward_out, uint8_t* done_out, int8_t* winner_out, int32_t* scores_out, uint8_t* status_out, void* stream);
 
 #ifdef __cplusplus
 }

@@ -38,29 +38,31 @@ def step_kernel(name, form):
     # evg_step_kernel<OT, 64, MULTI, MT, CHUNKED, SEAT>: the keyed-draw instantiations (MT = false) of the form's MULTI, plain or chunked; the learner form
     # runs SEAT = true
     if form == "learner":
-        return re.search(r"evg_step_kernel<%s, 64, false, false, false, true(, 1(, false)?)?>" % dtype, name) is not None
+        return re.search(r"evg_step_kernel<%s, 64, false, false, false, true(, 1(, false(, false)?)?)?>" % dtype, name) is not None
     # (round 5: a seventh template parameter, wavefronts per workgroup -- 1 in every product instantiation; then an eighth, the Q form of the one-seat
-    # kernel -- false everywhere but in evg_step_vs_policy_smart_q's)
-    if re.search(r"evg_step_kernel<%s, 64, %s, false, (true|false), false(, 1(, false)?)?>" % (dtype, multi), name):
+    # kernel -- false everywhere but in evg_step_vs_policy_smart_q's; then a ninth, the league forms of the one-seat kernel -- false everywhere but in
+    # evg_step_vs_league(_q)'s)
+    if re.search(r"evg_step_kernel<%s, 64, %s, false, (true|false), false(, 1(, false(, false)?)?)?>" % (dtype, multi), name):
         return True
     return "evg_step4_kernel<%s, %s" % (dtype, multi) in name
 
 
 # The step-kernel forms the launchers name (csrc/evg_kernels.hip: SingleTurn, Persistent, ...): what each sets of evg_step_kernel's template parameters
-# <OT, LPW, MULTI, MT, CHUNKED, SEAT, WPB, QDEC>, after the observation type
-STEP_FORMS = {"single_turn": (64, 0, 0, 0, 0, 1, 0), "persistent": (64, 1, 0, 0, 0, 1, 0), "chunked": (64, 1, 0, 1, 0, 1, 0),
-              "stock_entropy": (64, 0, 1, 0, 0, 1, 0), "seat": (64, 0, 0, 0, 1, 1, 0), "seat_q": (64, 0, 0, 0, 1, 1, 1),
-              "two_seat_q": (64, 0, 0, 0, 0, 1, 1),
+# <OT, LPW, MULTI, MT, CHUNKED, SEAT, WPB, QDEC, LEAGUE>, after the observation type
+STEP_FORMS = {"single_turn": (64, 0, 0, 0, 0, 1, 0, 0), "persistent": (64, 1, 0, 0, 0, 1, 0, 0), "chunked": (64, 1, 0, 1, 0, 1, 0, 0),
+              "stock_entropy": (64, 0, 1, 0, 0, 1, 0, 0), "seat": (64, 0, 0, 0, 1, 1, 0, 0), "seat_q": (64, 0, 0, 0, 1, 1, 1, 0),
+              "two_seat_q": (64, 0, 0, 0, 0, 1, 1, 0), "seat_league": (64, 0, 0, 0, 1, 1, 0, 1), "seat_q_league": (64, 0, 0, 0, 1, 1, 1, 1),
               # diagnostic libraries only
-              "helper_lanes": (32, 0, 0, 0, 0, 1, 0), "helper_lanes_persistent": (32, 1, 0, 0, 0, 1, 0), "wg256": (64, 0, 0, 0, 0, 4, 0)}
+              "helper_lanes": (32, 0, 0, 0, 0, 1, 0, 0), "helper_lanes_persistent": (32, 1, 0, 0, 0, 1, 0, 0), "wg256": (64, 0, 0, 0, 0, 4, 0, 0)}
 OBS_MANGLED = {"float32": "f", "float64": "d", "int16": "s"}
 
 
 def step_kernel_symbol(form, obs_dtype="float32"):
     """the mangled symbol of a step-kernel form (a key of STEP_FORMS) for an observation type: what nm, the device assembly and the compiler's
     resource-usage remarks call it"""
-    lpw, multi, mt, chunked, seat, wpb, qdec = STEP_FORMS[form]
-    return "_ZN3evg15evg_step_kernelI%sLi%dELb%dELb%dELb%dELb%dELi%dELb%dEEEvNS_8StepArgsE" % (OBS_MANGLED[obs_dtype], lpw, multi, mt, chunked, seat, wpb, qdec)
+    lpw, multi, mt, chunked, seat, wpb, qdec, league = STEP_FORMS[form]
+    return "_ZN3evg15evg_step_kernelI%sLi%dELb%dELb%dELb%dELb%dELi%dELb%dELb%dEEEvNS_8StepArgsE" % (OBS_MANGLED[obs_dtype], lpw, multi, mt, chunked, seat, wpb,
+                                                                                                         qdec, league)
 
 
 def counter_rows(directory, form):
