@@ -195,6 +195,21 @@
         if (nvalid == EPW) {
             // full workgroup (wave-uniform): straight-line batches of 8 LDS reads, then 8 convert + store, no bounds checks
             constexpr int FULL = NVEC / WG, REM = NVEC % WG, BATCH = 8;
+            // Store v of a lane lies v KiB behind its first one: scalar base (the wave's output pointer) + a 32-bit lane offset formed once per batch of eight
+            // (`lane * VB + the batch's middle`) + the store's distance from that middle, -4 .. +3 KiB, in the instruction's 13-bit signed immediate.
+            // (-DEVG_NO_OBS_BASE, `make noobsbase`: per-store int indexing, three address instructions per store, for the A/B.)
+#ifdef EVG_NO_OBS_BASE
+            auto dst_of = [&](int v) -> OT* { return out + (lane + v * WG) * EP; };
+#else
+            constexpr int VB = EP * (int)sizeof(OT);                   // bytes per lane and store
+            char* const out_b = reinterpret_cast<char*>(out);          // wave-uniform
+            const uint32_t lane_b = (uint32_t)lane * (uint32_t)VB;
+            auto dst_of = [&](int v) -> OT* {
+                const int mid = (v / BATCH) * BATCH + BATCH / 2;         // the batch's stores lie -4 .. +3 KiB around its middle
+                const uint32_t off = lane_b + (uint32_t)(mid * WG * VB);
+                return reinterpret_cast<OT*>(out_b + off + (ptrdiff_t)(v - mid) * (WG * VB));
+            };
+#endif
 #pragma unroll
             for (int b0 = 0; b0 < FULL; b0 += BATCH) {
                 int vals[BATCH][EP];
@@ -203,12 +218,12 @@
                     if (b0 + j < FULL) unpack((lane + (b0 + j) * WG) * EP, vals[j]);
 #pragma unroll
                 for (int j = 0; j < BATCH; ++j)
-                    if (b0 + j < FULL) store_obs_vec<OT>(out + (lane + (b0 + j) * WG) * EP, vals[j]);
+                    if (b0 + j < FULL) store_obs_vec<OT>(dst_of(b0 + j), vals[j]);
             }
             if (REM && lane < REM) {
                 int vals[EP];
                 unpack((lane + FULL * WG) * EP, vals);
-                store_obs_vec<OT>(out + (lane + FULL * WG) * EP, vals);
+                store_obs_vec<OT>(dst_of(FULL), vals);
             }
         } else {
             for (int v = lane; v < NVEC; v += WG) {            // last, partial workgroup of the grid

@@ -55,6 +55,8 @@ __global__ void __launch_bounds__(64) k(uint32_t* out, int iters, uint32_t seed)
 #define X27(i) asm volatile("v_min_u32 %0, %0, %1" : "+v"(r[i]) : "v"(s1));
 #define X28(i) asm volatile("v_lshl_add_u64 %0, %0, 2, %1" : "+v"(q[i]) : "v"(q[(i + 1) & 7]));
 #define X29(i) asm volatile("v_mad_u32_u24 %0, %0, %1, %2" : "+v"(r[i]) : "v"(s1), "v"(seed));
+#define X30(i) asm volatile("v_bitop3_b32 %0, %0, %1, %2 bitop3:0x96" : "+v"(r[i]) : "v"(s1), "v"(seed));
+#define X31(i) asm volatile("v_bitop3_b32 %0, %0, %1, %2 bitop3:0x96" : "+v"(r[i]) : "v"(s1), "s"(seed));
             if (MODE == 0) { REP8(X0) } else if (MODE == 1) { REP8(X1) } else if (MODE == 2) { REP8(X2) } else if (MODE == 3) { REP8(X3) }
             else if (MODE == 4) { REP8(X4) } else if (MODE == 5) { REP8(X5) } else if (MODE == 6) { REP8(X6) } else if (MODE == 7) { REP8(X7) }
             else if (MODE == 8) { REP8(X8) } else if (MODE == 9) { REP8(X9) } else if (MODE == 10) { REP8(X10) } else if (MODE == 11) { REP8(X11) }
@@ -62,7 +64,7 @@ __global__ void __launch_bounds__(64) k(uint32_t* out, int iters, uint32_t seed)
             else if (MODE == 16) { REP8(X16) } else if (MODE == 17) { REP8(X17) } else if (MODE == 18) { REP8(X18) } else if (MODE == 19) { REP8(X19) }
             else if (MODE == 20) { REP8(X20) } else if (MODE == 21) { REP8(X21) } else if (MODE == 22) { REP8(X22) } else if (MODE == 23) { REP8(X23) }
             else if (MODE == 24) { REP8(X24) } else if (MODE == 25) { REP8(X25) } else if (MODE == 26) { REP8(X26) } else if (MODE == 27) { REP8(X27) }
-            else if (MODE == 28) { REP8(X28) } else { REP8(X29) }
+            else if (MODE == 28) { REP8(X28) } else if (MODE == 29) { REP8(X29) } else if (MODE == 30) { REP8(X30) } else { REP8(X31) }
         }
         if (MODE == 23) asm volatile("s_waitcnt lgkmcnt(0)");
     }
@@ -79,17 +81,17 @@ template <> struct Tab<-1> { static void fill(kern_t*) {} };
 
 int main() {
     uint32_t* dmem; hipMalloc(&dmem, ((1 << 20) + 16) * 4);
-    const char* names[30] = {"v_add_u32", "v_mul_lo_u32", "v_mul_hi_u32", "v_mul_u32_u24", "v_mad_u64_u32", "v_lshlrev_b64", "v_fma_f64", "v_add_f64", "v_mul_f64",
+    const char* names[32] = {"v_add_u32", "v_mul_lo_u32", "v_mul_hi_u32", "v_mul_u32_u24", "v_mad_u64_u32", "v_lshlrev_b64", "v_fma_f64", "v_add_f64", "v_mul_f64",
                              "v_cmp_ge_f64", "v_cvt_f64_u32", "v_perm_b32", "v_bcnt_u32_b32", "v_cndmask_b32", "v_lshrrev_b64 (var)", "v_xor_b32", "v_mov_b32 dpp quad_perm",
                              "v_cvt_f32_i32 sdwa", "v_or3_b32", "v_lshl_add_u32", "v_alignbyte_b32", "v_bfe_u32", "s_add_u32", "ds_read_b32 (+wait per 32)", "ds_write_b32",
-                             "ds_add_u32", "v_max_f64", "v_min_u32", "v_lshl_add_u64", "v_mad_u32_u24"};
-    kern_t tab[30];
-    Tab<29>::fill(tab);
+                             "ds_add_u32", "v_max_f64", "v_min_u32", "v_lshl_add_u64", "v_mad_u32_u24", "v_bitop3_b32 0x96 (v, v, v)", "v_bitop3_b32 0x96 (v, v, s)"};
+    kern_t tab[32];
+    Tab<31>::fill(tab);
     const int iters = 20000;
     for (int wps = 1; wps <= 4; wps *= 2) {
         const int grid = 1024 * wps;             // 1024 SIMDs
         printf("---- %d wave(s) per SIMD (%d workgroups of 64)\n", wps, grid);
-        for (int m = 0; m < 30; ++m) {
+        for (int m = 0; m < 32; ++m) {
             hipEvent_t e0, e1; hipEventCreate(&e0); hipEventCreate(&e1);
             float ms = 0;
             for (int rep = 0; rep < 2; ++rep) {
