@@ -10,14 +10,14 @@ from ._lib import EvgError, EvgFault, load as load_library
 from .tables import default_tables, tables_from_json
 from .vec_env import EvergladesVecEnv
 from .replay import SmartReplay
-from .qnet import SmartQNet
+from .qnet import MinimizedQNet, SmartQNet
 from .league import OpponentLeague
 from .pipeline import PipelinedVecEnv
 from .env import EvergladesEnv, canonical_actions
 from .distributed import shard_range, gather_episode_results, win_counts, ResultGather, NativeGather
 from .harness import evaluate, evaluate_all, proportion_confint_normal
 
-__all__ = ["EvergladesVecEnv", "SmartReplay", "SmartQNet", "OpponentLeague", "PipelinedVecEnv", "EvergladesEnv", "EvgError", "EvgFault", "load_library", "default_tables", "tables_from_json",
+__all__ = ["EvergladesVecEnv", "SmartReplay", "SmartQNet", "MinimizedQNet", "OpponentLeague", "PipelinedVecEnv", "EvergladesEnv", "EvgError", "EvgFault", "load_library", "default_tables", "tables_from_json",
            "canonical_actions", "shard_range", "gather_episode_results", "win_counts", "ResultGather", "NativeGather", "evaluate", "evaluate_all",
            "proportion_confint_normal"]
 

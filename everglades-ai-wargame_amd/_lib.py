@@ -30,6 +30,7 @@ EXPORTS = ["evg_default_tables", "evg_create", "evg_destroy", "evg_reset", "evg_
            "evg_step_vs_policy_smart_q", "evg_step_smart_q", "evg_replay_clear", "evg_replay_record", "evg_replay_size", "evg_replay_sample",
            "evg_replay_gather", "evg_smart_qnet",
            "evg_league_clear", "evg_league_assign", "evg_league_importance", "evg_step_vs_league", "evg_step_vs_league_q",
+           "evg_minimized_get_action", "evg_step_vs_policy_minimized_q", "evg_step_vs_league_minimized_q", "evg_minimized_qnet",
            "evg_observe_seat",
            "evg_random_actions_seat", "evg_smart_state_seat", "evg_smart_state_compact", "evg_check_fault", "evg_rollout_vs_policy", "evg_fog_of_war",
            "evg_sightings", "evg_smart_state", "evg_smart_actions", "evg_smart_get_action", "evg_move_table", "evg_random_actions", "evg_rollout_random", "evg_rollout_policies",
@@ -111,6 +112,14 @@ class EvgQnet(C.Structure):
     ]
 
 
+class EvgMiniQnet(C.Structure):
+    """evg_mini_qnet of include/evg.h: the Minimized Q network's weights (device pointers the caller owns, nn.Linear layout), one or two sets."""
+    _fields_ = [
+        ("struct_size", C.c_uint32), ("h1", C.c_int32), ("final_relu", C.c_int32), ("num_sets", C.c_int32),
+        ("w1", C.c_void_p * 2), ("b1", C.c_void_p * 2), ("w2", C.c_void_p * 2), ("b2", C.c_void_p * 2),
+    ]
+
+
 class EvgLeague(C.Structure):
     """evg_league of include/evg.h: the descriptor of an opponent league (device pointers the caller owns)."""
     _fields_ = [
@@ -124,6 +133,7 @@ LEAGUE_S_BAD_WEIGHTS, LEAGUE_S_BAD_ASSIGN = 1, 2              # EVG_LEAGUE_S_*
 ERR_ARG = -1          # EVG_ERR_ARG (= EVG_ERR_INVALID): a bad argument, e.g. a league descriptor out of range
 QNET_COMPACT, QNET_COMPACT_SEATS, QNET_EXPANDED = 0, 1, 2     # EVG_QNET_*
 QNET_MAX_HIDDEN, QNET_MAX_ROWS = 64, 1 << 30
+MINI_QNET_MAX_HIDDEN, MINI_QNET_OUT = 128, 11                  # EVG_MINI_QNET_MAX_HIDDEN; the Minimized head: one Q per node
 
 
 SHAPE_NAMES = ["normalized_score", "basic_reward", "penalize_long_games", "reward_short_games", "transition", "custom"]   # index = EVG_SHAPE_*
@@ -216,6 +226,10 @@ def load(path=None):
     L.evg_league_importance.argtypes = [vp, lp, vp, vp]
     L.evg_step_vs_league.argtypes = [vp, vp, C.c_int, lp, vp, vp, vp, vp, vp, vp, vp, vp, vp]
     L.evg_step_vs_league_q.argtypes = [vp, vp, C.c_float, vp, lp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]
+    L.evg_minimized_get_action.argtypes = [vp, vp, C.c_float, vp, C.c_int, vp, vp, vp]
+    L.evg_step_vs_policy_minimized_q.argtypes = [vp, C.c_int, vp, C.c_float, vp, C.c_int, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]
+    L.evg_step_vs_league_minimized_q.argtypes = [vp, vp, C.c_float, vp, lp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]
+    L.evg_minimized_qnet.argtypes = [vp, C.POINTER(EvgMiniQnet), C.c_int, C.c_int64, vp, vp, vp, vp]
     L.evg_random_actions_seat.argtypes = [vp, C.c_int, vp, vp]
     L.evg_smart_state_seat.argtypes = [vp, vp, vp, vp]
     L.evg_smart_state_compact.argtypes = [vp, C.c_int, vp, vp, vp, vp]

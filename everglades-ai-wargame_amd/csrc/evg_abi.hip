@@ -1064,6 +1064,90 @@ int evg_step_vs_league_q(evg_handle* h, const float* q, float epsilon, const flo
     return launched("step", launch_step_league(h->S, io, h->cfg.obs_dtype, h->caps, stream));
 } catch (...) { return on_exception(); }
 
+// ---- the Minimized agents (include/evg.h: evg_minimized_get_action, evg_step_vs_*_minimized_q, evg_minimized_qnet) ----
+int evg_minimized_get_action(evg_handle* h, const float* q, float epsilon, const float* epsilon_env, int seat, int32_t* actions_out, uint8_t* explored_out,
+                             void* stream) try {
+    if (!h || !q || !actions_out || seat < 0 || seat > 1) return fail(EVG_ERR_INVALID, "bad argument");
+    if (const int rc = check_epsilon(epsilon, epsilon_env)) return rc;
+    EVG_NEED_ALIGNED16(q); EVG_NEED_ALIGNED16(actions_out);
+    if (const int rc = check_keyed_philox(h, "evg_minimized_get_action", " (the agent's draws are keyed)")) return rc;
+    EVG_ON_DEVICE(h);
+    const SmartExplore ex{seat, epsilon, epsilon_env, explored_out};
+    const bool greedy = !epsilon_env && epsilon == 0.0f;
+    return launched("minimized_get_action", launch_minimized_actions(h->S, q, actions_out, stream, greedy ? nullptr : &ex, explored_out));
+} catch (...) { return on_exception(); }
+
+int evg_step_vs_policy_minimized_q(evg_handle* h, int seat, const float* q, float epsilon, const float* epsilon_env, int opponent_policy, void* obs_seat_out,
+                                   float* shared_out, float* swarm_out, int32_t* actions_out, uint8_t* explored_out, float* reward_out, uint8_t* done_out,
+                                   int8_t* winner_out, int32_t* scores_out, uint8_t* status_out, void* stream) try {
+    if (!h) return fail(EVG_ERR_INVALID, "null handle");
+    if (!q || !obs_seat_out || !reward_out || !done_out) return fail(EVG_ERR_INVALID, "q, obs_seat_out, reward_out and done_out are required");
+    if (const int rc = check_seat_and_opponent(seat, opponent_policy)) return rc;
+    if (const int rc = check_epsilon(epsilon, epsilon_env)) return rc;
+    if (const int rc = check_feature_pair(shared_out, swarm_out)) return rc;
+    EVG_NEED_ALIGNED16(q); EVG_NEED_ALIGNED16(obs_seat_out); EVG_NEED_ALIGNED16(shared_out); EVG_NEED_ALIGNED16(swarm_out);
+    EVG_NEED_ALIGNED16(actions_out); EVG_NEED_ALIGNED8(reward_out); EVG_NEED_ALIGNED8(scores_out);
+    if (const int rc = check_keyed_philox(h, "evg_step_vs_policy_minimized_q", " (the stock-entropy mode has no fused bots)")) return rc;
+    EVG_ON_DEVICE(h);
+    LaunchIO io(h);
+    io.obs = obs_seat_out;
+    io.reward = reward_out; io.done = done_out; io.winner = winner_out; io.scores = scores_out; io.status = status_out;
+    io.gen_actions = 2; io.policy0 = io.policy1 = opponent_policy;
+    io.seat = seat;
+    io.feat_shared = shared_out; io.feat_swarm = swarm_out;
+    io.q = q; io.eps = epsilon; io.eps_env = epsilon_env;
+    io.q_actions = actions_out; io.q_explored = explored_out;
+    return launched("step", launch_step_minimized(h->S, io, h->cfg.obs_dtype, h->caps, stream));
+} catch (...) { return on_exception(); }
+
+int evg_step_vs_league_minimized_q(evg_handle* h, const float* q, float epsilon, const float* epsilon_env, const evg_league* lg, void* obs_seat_out,
+                                   float* shared_out, float* swarm_out, int32_t* actions_out, uint8_t* explored_out, float* reward_out, uint8_t* done_out,
+                                   int8_t* winner_out, int32_t* scores_out, uint8_t* status_out, void* stream) try {
+    if (!h) return fail(EVG_ERR_INVALID, "null handle");
+    if (!q || !obs_seat_out || !reward_out || !done_out) return fail(EVG_ERR_INVALID, "q, obs_seat_out, reward_out and done_out are required");
+    { const int rc = check_league(h, lg); if (rc) return rc; }
+    if (const int rc = check_epsilon(epsilon, epsilon_env)) return rc;
+    if (const int rc = check_feature_pair(shared_out, swarm_out)) return rc;
+    EVG_NEED_ALIGNED16(q); EVG_NEED_ALIGNED16(obs_seat_out); EVG_NEED_ALIGNED16(shared_out); EVG_NEED_ALIGNED16(swarm_out);
+    EVG_NEED_ALIGNED16(actions_out); EVG_NEED_ALIGNED8(reward_out); EVG_NEED_ALIGNED8(scores_out);
+    EVG_ON_DEVICE(h);
+    LaunchIO io(h);
+    io.obs = obs_seat_out;
+    io.reward = reward_out; io.done = done_out; io.winner = winner_out; io.scores = scores_out; io.status = status_out;
+    league_io(io, lg);
+    io.feat_shared = shared_out; io.feat_swarm = swarm_out;
+    io.q = q; io.eps = epsilon; io.eps_env = epsilon_env;
+    io.q_actions = actions_out; io.q_explored = explored_out;
+    return launched("step", launch_step_minimized(h->S, io, h->cfg.obs_dtype, h->caps, stream));
+} catch (...) { return on_exception(); }
+
+int evg_minimized_qnet(evg_handle* h, const evg_mini_qnet* net, int layout, int64_t rows, const float* in0, const float* in1, float* q_out, void* stream) try {
+    if (!h || !net) return fail(EVG_ERR_INVALID, "null handle or network descriptor");
+    if (net->struct_size != sizeof(evg_mini_qnet))
+        return fail(EVG_ERR_INVALID, "minimized qnet: struct_size %u != sizeof(evg_mini_qnet) %zu", net->struct_size, sizeof(evg_mini_qnet));
+    if (net->h1 < 1 || net->h1 > EVG_MINI_QNET_MAX_HIDDEN)
+        return fail(EVG_ERR_INVALID, "minimized qnet: the hidden size must lie in 1..%d (got %d)", EVG_MINI_QNET_MAX_HIDDEN, net->h1);
+    if (net->final_relu != 0 && net->final_relu != 1) return fail(EVG_ERR_INVALID, "minimized qnet: final_relu must be 0 or 1 (got %d)", net->final_relu);
+    if (layout != EVG_QNET_COMPACT && layout != EVG_QNET_COMPACT_SEATS && layout != EVG_QNET_EXPANDED)
+        return fail(EVG_ERR_INVALID, "minimized qnet: unknown layout %d", layout);
+    const int sets = layout == EVG_QNET_COMPACT_SEATS ? 2 : 1;
+    if (net->num_sets != sets) return fail(EVG_ERR_INVALID, "minimized qnet: layout %d takes %d weight set(s) (got num_sets %d)", layout, sets, net->num_sets);
+    if (rows < 1 || rows > EVG_QNET_MAX_ROWS) return fail(EVG_ERR_INVALID, "minimized qnet: rows must lie in 1..2^30 (got %lld)", (long long)rows);
+    for (int p = 0; p < sets; ++p) {
+        const float* w[4] = {net->w1[p], net->b1[p], net->w2[p], net->b2[p]};
+        static const char* names[4] = {"w1", "b1", "w2", "b2"};
+        for (int i = 0; i < 4; ++i) {
+            if (!w[i]) return fail(EVG_ERR_INVALID, "minimized qnet: %s[%d] is NULL", names[i], p);
+            if (misaligned16(w[i])) return fail(EVG_ERR_INVALID, "minimized qnet: %s[%d] must be 16-byte aligned (got %p)", names[i], p, (const void*)w[i]);
+        }
+    }
+    if (!in0 || !q_out || (layout != EVG_QNET_EXPANDED && !in1))
+        return fail(EVG_ERR_INVALID, "minimized qnet: in0, q_out and (compact layouts) in1 are required");
+    EVG_NEED_ALIGNED16(in0); EVG_NEED_ALIGNED16(in1); EVG_NEED_ALIGNED16(q_out);
+    EVG_ON_DEVICE(h);
+    return launched("minimized qnet", launch_minimized_qnet(*net, layout, (long long)rows, in0, in1, q_out, h->caps.cus, stream));
+} catch (...) { return on_exception(); }
+
 void evg_move_table(int32_t* table /* [11][5] */) {
     // agents/Smart_State/Move_Translation.py:3-97: node reached from (0-indexed) node n0 in direction 0 left, 1 right, 2 up, 3 down, 4 stay
     static const int32_t T[5][11] = {{1, 1, 3, 1, 2, 3, 4, 5, 6, 7, 11}, {1, 5, 6, 7, 8, 9, 10, 11, 9, 11, 11}, {2, 2, 2, 3, 5, 6, 7, 8, 8, 9, 8},

@@ -237,5 +237,10 @@ int launch_replay_gather(const DevState& S, const evg_replay& m, int batch, cons
                          float* reward, uint8_t* not_done, void* stream);
 // the Smart_State Q network's forward pass (qnet_kernels.inc); `net` and the sizes are validated by the caller (evg_abi.hip)
 int launch_smart_qnet(const evg_qnet& net, int layout, long long rows, const float* in0, const float* in1, float* q_out, int num_cu, void* stream);
+// the Minimized agents' decode and Q network (minimized_decode.inc, minimized_qnet.inc); arguments validated by the caller (evg_abi.hip)
+int launch_step_minimized(const DevState& S, const StepIO& io, int obs_dtype, const DeviceCaps& caps, void* stream);
+int launch_minimized_actions(const DevState& S, const float* q, int32_t* actions, void* stream, const SmartExplore* explore /* NULL: get_best_actions only */,
+                             uint8_t* explored /* device [N] or NULL */);
+int launch_minimized_qnet(const evg_mini_qnet& net, int layout, long long rows, const float* in0, const float* in1, float* q_out, int num_cu, void* stream);
 
 }  // namespace evg

@@ -66,6 +66,7 @@ namespace evg {
 #include "step_agents.inc"      // the scripted opponents (one device function over a view)
 #include "league_choice.inc"    // the opponent league's member draw and object swap (the step kernel's league forms and league_kernels.inc)
 #include "smart_decode.inc"     // the Smart_State agent's decode of its Q values (the standalone kernel and the step kernel's Q form)
+#include "minimized_decode.inc" // the Minimized agents' decode of their 11-way Q values (the standalone kernel and the step kernel's 11-way Q forms)
 #include "step_kernel.inc"      // evg_step_kernel: skeleton + the phases of a turn (step_orders / step_combat / step_move_capture / step_outputs .inc)
 
 #include "evg_step4.inc"        // the four-lanes-per-env mapping: what persistent launches of SMALL batches run (launch_step)
@@ -77,6 +78,7 @@ namespace evg {
 #include "replay_kernels.inc"   // the Smart_State learner's n-step replay memory: record, count, draw, gather
 #include "qnet_kernels.inc"     // the Smart_State Q network's forward pass (inference) on v_mfma_f32_16x16x4_f32
 #include "league_kernels.inc"   // the opponent league: clear, assign after an explicit reset, importance weights
+#include "minimized_qnet.inc"   // the Minimized agents' Q network's forward pass (59 -> h1 <= 128 -> 11) on v_mfma_f32_16x16x4_f32
 
 // ---------------------------------------------------------------------------------------------
 // launchers
@@ -104,6 +106,7 @@ struct SingleTurn {                                  // one turn per launch, 32 
     static constexpr int waves_per_block = 1;        // WPB: independent wavefronts per workgroup
     static constexpr bool qdec = false;              // QDEC: orders decoded in the launch from the Q values io.q
     static constexpr bool league = false;            // LEAGUE: the scripted policy of the other seat is a per-env member of an opponent league (io.lg_*)
+    static constexpr int head = HEAD_SMART;          // HEAD: the agent family whose network output a Q form decodes (HEAD_MINIMIZED: evg_step_minimized_kernel)
 };
 struct Persistent : SingleTurn { static constexpr bool multi = true; };
 struct Chunked : Persistent { static constexpr bool chunked = true; };
@@ -113,16 +116,22 @@ struct SeatQ : Seat { static constexpr bool qdec = true; };
 struct TwoSeatQ : SingleTurn { static constexpr bool qdec = true; };
 struct SeatLeague : Seat { static constexpr bool league = true; };
 struct SeatQLeague : SeatQ { static constexpr bool league = true; };
+struct SeatQMin : SeatQ { static constexpr int head = HEAD_MINIMIZED; };
+struct SeatQMinLeague : SeatQMin { static constexpr bool league = true; };
 #ifdef EVG_DIAG
 // diagnostic library, lanes = 32: 16 envs per wavefront + 32 helper lanes, in both launch forms
 template <typename Form> struct HelperLanes : Form { static constexpr int lanes = WG / 2; };
 struct Wg256 : SingleTurn { static constexpr int waves_per_block = 4; };
 #endif
 // (OT, form) -> the kernel, e.g. SeatQ with float32 observations: evg_step_kernel<float, 64, false, false, false, true, 1, true, false>
+// (the 11-way head: evg_step_minimized_kernel<OT, LEAGUE>, a kernel of its own name -- step_kernel.inc)
 template <typename OT, typename Form>
-constexpr auto step_kernel_of =
-    evg_step_kernel<OT, Form::lanes, Form::multi, Form::stock_mt, Form::chunked, Form::seat, Form::waves_per_block, Form::qdec,
-                    Form::league>;
+constexpr auto step_kernel_of_head() {
+    if constexpr (Form::head == HEAD_MINIMIZED) return evg_step_minimized_kernel<OT, Form::league>;
+    else return evg_step_kernel<OT, Form::lanes, Form::multi, Form::stock_mt, Form::chunked, Form::seat, Form::waves_per_block, Form::qdec, Form::league>;
+}
+template <typename OT, typename Form>
+constexpr auto step_kernel_of = step_kernel_of_head<OT, Form>();
 
 // One launch of a step-kernel form over envs [io.env_lo, io.env_hi): a wavefront per set of envs -- the chunked form: as many workgroups as the device holds
 // (io.grid_slots), each taking units from its XCD's queue
@@ -426,6 +435,31 @@ int launch_smart_actions(const DevState& S, int player, const void* obs, int sea
         else hipLaunchKernelGGL((evg_smart_actions_kernel<OT, false>), grid, block, 0, s, S.N, player, seat_only, (const OT*)obs, q, a, d, X);
         return (int)hipGetLastError();
     });
+}
+
+// evg_step_vs_policy_minimized_q / evg_step_vs_league_minimized_q: the one-seat Q form with the 11-way head (io.lg_assign: its league form)
+int launch_step_minimized(const DevState& S, const StepIO& io_in, int obs_dtype, const DeviceCaps& caps, void* stream) {
+    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+    if (S.mt_key || !io_in.q) return -1;
+    const StepIO io = single_turn_io(S, io_in, caps);
+    return io.lg_assign ? launch_form<SeatQMinLeague>(S, io, obs_dtype, s) : launch_form<SeatQMin>(S, io, obs_dtype, s);
+}
+
+// the Minimized agents' network output -> orders: one DPP row (16 lanes) per env; ex NULL: get_best_actions only
+int launch_minimized_actions(const DevState& S, const float* q, int32_t* actions, void* stream, const SmartExplore* ex, uint8_t* explored) {
+    const unsigned threads = ex ? 1024u : 256u;
+    const dim3 grid((unsigned)(((size_t)S.N * 16 + threads - 1) / threads)), block(threads);
+    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+    int2* a = reinterpret_cast<int2*>(actions);
+    ExploreArgs X{};
+    X.explored = explored;
+    if (ex) {
+        X = ExploreArgs{S.seed_lo, S.seed_hi, S.env_id_base, S.episode, ex->seat, ex->eps, ex->eps_env, explored};
+        hipLaunchKernelGGL(evg_minimized_actions_kernel<true>, grid, block, 0, s, S.N, S.env, q, a, X);
+    } else {
+        hipLaunchKernelGGL(evg_minimized_actions_kernel<false>, grid, block, 0, s, S.N, S.env, q, a, X);
+    }
+    return (int)hipGetLastError();
 }
 
 int launch_fog(const DevState& S, uint8_t* fog, uint8_t* know, int8_t* sight, void* stream) {

@@ -388,3 +388,40 @@ __global__ void __launch_bounds__(EXPLORE ? 1024 : 256) evg_smart_actions_kernel
         if (directions) directions[(size_t)e * NA + rank] = make_int2(s, dir);
     }
 }
+
+// ---------------------------------------------------------------------------------------------
+// The Minimized agent's network output -> orders: DQNAgent.get_action of agents/Minimized/DQNAgent.py:121-242 (evg_minimized_get_action).  q [N][12][11]
+// float32 is the policy network's output for every swarm, one Q per node; the rules are minimized_decode.inc's, the mapping evg_smart_actions_kernel's: one
+// DPP row (16 lanes) per env, lane = swarm, and -- EXPLORE -- the first wavefront of a 1 024-thread workgroup draws for the workgroup's 64 envs.  The
+// agent reads no observation: the turn that keys its draws is the handle's (what obs[0] of the env shows).  EXPLORE = false is get_best_actions alone.
+// ---------------------------------------------------------------------------------------------
+template <bool EXPLORE>
+__global__ void __launch_bounds__(EXPLORE ? 1024 : 256) evg_minimized_actions_kernel(int N, const uint32_t* __restrict__ envw, const float* __restrict__ q,
+                                                                                    int2* __restrict__ actions, ExploreArgs X) {
+    constexpr int BLOCK = EXPLORE ? 1024 : 256;
+    const int t = blockIdx.x * BLOCK + threadIdx.x;
+    const int e = t >> 4, s = t & 15;
+    [[maybe_unused]] __shared__ uint32_t draws[EXPLORE ? BLOCK / 16 : 1][2];
+    uint2 d = make_uint2(0u, 0u);
+    if constexpr (EXPLORE) {
+        const int ed = blockIdx.x * (BLOCK / 16) + (int)threadIdx.x;             // the first wavefront: lane = env of this workgroup
+        if (threadIdx.x < BLOCK / 16 && ed < N) {
+            const int turn = (int)(envw[ed] & 0xFFu);
+            const uint32_t env_id = X.env_id_base + (uint32_t)ed, episode = X.episode[ed];
+            const uint4 b0 = rng_block(X.seed_lo, X.seed_hi, env_id, episode, RNG_EXPLORE, 0u, turn, 0, X.seat, 0);
+            const uint4 b1 = rng_block(X.seed_lo, X.seed_hi, env_id, episode, RNG_EXPLORE, 1u, turn, 0, X.seat, 0);
+            const uint2 w = minimized_explore_words(b0, b1, X.eps_env ? X.eps_env[ed] : X.eps);
+            if (X.explored) X.explored[ed] = (w.x >> 31) ? 1 : 0;
+            draws[threadIdx.x][0] = w.x;
+            draws[threadIdx.x][1] = w.y;
+        }
+        __syncthreads();
+        d = make_uint2(draws[threadIdx.x >> 4][0], draws[threadIdx.x >> 4][1]);
+    } else {
+        if (X.explored && s == 0 && e < N) X.explored[e] = 0;
+    }
+    const bool act = e < N && s < NG;
+    int node;
+    const int rank = minimized_decide(q + (size_t)(e < N ? e : 0) * (NG * MIN_Q), act, e < N, s, d, node);
+    if (act && rank < NA) actions[(size_t)e * NA + rank] = make_int2(s, node);
+}

@@ -60,6 +60,8 @@ def _param_source(net, final_relu):
 
 
 class SmartQNet(object):
+    OUT = 5                                               # width of the head
+
     def __init__(self, env, net, final_relu=None):
         torch = _torch()
         self.env, self.L = env, env.L
@@ -129,10 +131,12 @@ class SmartQNet(object):
         if not 1 <= rows <= _lib.QNET_MAX_ROWS:
             raise ValueError("rows must lie in 1..2^30 (got %d)" % rows)
         d = self._descriptor(sets)
-        rc = self.L.evg_smart_qnet(self.env._h, C.byref(d), layout, rows, C.c_void_p(in0.data_ptr()),
-                                   None if in1 is None else C.c_void_p(in1.data_ptr()), C.c_void_p(out.data_ptr()), self.env._stream())
-        self.env._check(rc)
+        self.env._check(self._launch(d, layout, rows, in0, in1, out))
         return out
+
+    def _launch(self, d, layout, rows, in0, in1, out):
+        return self.L.evg_smart_qnet(self.env._h, C.byref(d), layout, rows, C.c_void_p(in0.data_ptr()),
+                                     None if in1 is None else C.c_void_p(in1.data_ptr()), C.c_void_p(out.data_ptr()), self.env._stream())
 
     def __call__(self, shared, swarm, out=None):
         """Q from the compact features: shared [N, 34] and swarm [N, 12, 13] -> [N, 12, 5] (one network), or shared [N, 2, 34] and swarm [N, 2, 12, 13]
@@ -148,9 +152,9 @@ class SmartQNet(object):
         self._input(shared, lead + (34,), "shared")
         self._input(swarm, lead + (12, 13), "swarm")
         if out is None:
-            out = torch.empty(lead + (12, 5), dtype=torch.float32, device=self.env.device)
+            out = torch.empty(lead + (12, self.OUT), dtype=torch.float32, device=self.env.device)
         else:
-            self._input(out, lead + (12, 5), "out")
+            self._input(out, lead + (12, self.OUT), "out")
         layout = _lib.QNET_COMPACT_SEATS if seats else _lib.QNET_COMPACT
         return self._run(layout, 2 if seats else 1, N, shared, swarm, out)
 
@@ -164,9 +168,95 @@ class SmartQNet(object):
             raise ValueError("x must be a float32 tensor [..., 59]")
         self._input(x, tuple(x.shape), "x")
         rows = x.numel() // 59
-        shape = tuple(x.shape[:-1]) + (5,)
+        shape = tuple(x.shape[:-1]) + (self.OUT,)
         if out is None:
             out = torch.empty(shape, dtype=torch.float32, device=self.env.device)
         else:
             self._input(out, shape, "out")
         return self._run(_lib.QNET_EXPANDED, 1, rows, x, None, out)
+
+
+def _mini_param_source(net, final_relu):
+    """-> (a function returning the 4 tensors as they are now, final_relu)."""
+    torch = _torch()
+    if isinstance(net, (tuple, list)) and len(net) == 4 and all(isinstance(t, torch.Tensor) for t in net):
+        if final_relu is None:
+            raise ValueError("a tuple of weights needs final_relu=True or False")
+        ts = tuple(net)
+        return (lambda: ts), bool(final_relu)
+    if isinstance(net, torch.nn.Sequential):
+        mods = list(net)
+        kinds = [type(m) for m in mods]
+        lin, relu = torch.nn.Linear, torch.nn.ReLU
+        if kinds[:3] != [lin, relu, lin] or not (len(mods) == 3 or (len(mods) == 4 and kinds[3] is relu)):
+            raise ValueError("an nn.Sequential must be Linear, ReLU, Linear[, ReLU]")
+        inferred = len(mods) == 4
+        if final_relu is not None and bool(final_relu) != inferred:
+            raise ValueError("final_relu=%s contradicts the Sequential (%s final ReLU)" % (final_relu, "with" if inferred else "without"))
+        for i in (0, 2):
+            _linear_params(mods[i], "layer %d" % i)
+        return (lambda: (mods[0].weight, mods[0].bias, mods[2].weight, mods[2].bias)), inferred
+    if all(hasattr(net, a) for a in ("fc1", "fc2")) and not hasattr(net, "fc3"):      # the reference's Minimized QNetwork: final ReLU on
+        for a in ("fc1", "fc2"):
+            _linear_params(getattr(net, a), a)
+        return (lambda: (net.fc1.weight, net.fc1.bias, net.fc2.weight, net.fc2.bias)), True if final_relu is None else bool(final_relu)
+    raise ValueError("net must be a Minimized QNetwork (fc1/fc2), an nn.Sequential of Linear/ReLU/Linear[/ReLU], a 4-tuple of tensors, or a pair")
+
+
+class MinimizedQNet(SmartQNet):
+    """The Minimized agents' Q network on the device, one launch (include/evg.h, evg_minimized_qnet): agents/Minimized/QNetwork.py,
+    relu(fc2(relu(fc1(x)))), 59 -> h1 -> 11 with h1 in 1..128.  SmartQNet's contract -- parameters read in place on every call, the fmaf-chain numerics,
+    no autograd, no host synchronisation -- and its calls: qnet(shared, swarm) -> [N, 12, 11] or [N, 2, 12, 11], qnet.expanded(x [..., 59]) -> [..., 11]."""
+    OUT = _lib.MINI_QNET_OUT
+
+    def __init__(self, env, net, final_relu=None):
+        self.env, self.L = env, env.L
+        pair = isinstance(net, (tuple, list)) and len(net) == 2
+        nets = list(net) if pair else [net]
+        srcs = [_mini_param_source(n, final_relu) for n in nets]
+        if len({fr for _, fr in srcs}) != 1:
+            raise ValueError("the two networks of a pair must agree on the final ReLU")
+        self._srcs = [s for s, _ in srcs]
+        self.pair = pair
+        self.final_relu = srcs[0][1]
+        shapes = [self._params(p)[1] for p in range(len(self._srcs))]
+        if len(set(shapes)) != 1:
+            raise ValueError("the two networks of a pair must have the same hidden size (got %s)" % (shapes,))
+        self.h1 = shapes[0]
+        self._d = _lib.EvgMiniQnet()
+        self._d.struct_size = C.sizeof(_lib.EvgMiniQnet)
+
+    def _params(self, p):
+        """The 4 tensors of set p as they are now, checked: fp32, on the env's device, contiguous, 16-byte aligned, nn.Linear shapes."""
+        torch = _torch()
+        ts = self._srcs[p]()
+        for t, n in zip(ts, ("w1", "b1", "w2", "b2")):
+            if not isinstance(t, torch.Tensor) or t.dtype != torch.float32 or t.device != self.env.device or not t.is_contiguous():
+                raise ValueError("%s must be a contiguous float32 tensor on %s" % (n, self.env.device))
+            if t.data_ptr() % 16:
+                raise ValueError("%s must be 16-byte aligned" % n)
+        w1, b1, w2, b2 = ts
+        if w1.dim() != 2 or w1.shape[1] != 59 or not 1 <= w1.shape[0] <= _lib.MINI_QNET_MAX_HIDDEN:
+            raise ValueError("w1 must be [h1, 59] with h1 in 1..%d, got %s" % (_lib.MINI_QNET_MAX_HIDDEN, tuple(w1.shape)))
+        h1 = w1.shape[0]
+        if tuple(w2.shape) != (self.OUT, h1) or tuple(b1.shape) != (h1,) or tuple(b2.shape) != (self.OUT,):
+            raise ValueError("w2 [11, %d], b1 [%d], b2 [11] expected, got %s %s %s" % (h1, h1, tuple(w2.shape), tuple(b1.shape), tuple(b2.shape)))
+        return ts, h1
+
+    def _descriptor(self, sets):
+        d = self._d
+        for p in range(2):
+            ts, h1 = self._params(p if self.pair else 0)
+            if h1 != self.h1:
+                raise ValueError("the network's hidden size changed from %d to %d" % (self.h1, h1))
+            d.w1[p], d.b1[p], d.w2[p], d.b2[p] = (t.data_ptr() for t in ts)
+            if not self.pair:
+                break
+        if sets == 2 and not self.pair:               # the same set on both seats
+            d.w1[1], d.b1[1], d.w2[1], d.b2[1] = d.w1[0], d.b1[0], d.w2[0], d.b2[0]
+        d.h1, d.final_relu, d.num_sets = self.h1, int(self.final_relu), sets
+        return d
+
+    def _launch(self, d, layout, rows, in0, in1, out):
+        return self.L.evg_minimized_qnet(self.env._h, C.byref(d), layout, rows, C.c_void_p(in0.data_ptr()),
+                                         None if in1 is None else C.c_void_p(in1.data_ptr()), C.c_void_p(out.data_ptr()), self.env._stream())

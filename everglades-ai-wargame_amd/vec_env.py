@@ -257,12 +257,19 @@ class EvergladesVecEnv(object):
         network's output; `epsilon` a float in [0, 1] or a float32 tensor [N].  Returns (obs_seat [N, 105], reward [N, 2], done [N], info) like step_vs();
         bit-identical to smart_get_action(q, epsilon, seat, obs=<the previous seat observation>) + step_vs(policy, rows, seat).  features=(shared [N, 34],
         swarm [N, 12, 13]) as in step_vs() (shared 16-byte aligned); `directions` / `actions_out` int32 [N, 7, 2] receive {swarm, direction} / the rows
-        played, `explored` uint8 [N] 1 where the random branch ran.  No host synchronisation and no allocation per call: it can sit inside a captured loop."""
+        played, `explored` uint8 [N] 1 where the random branch ran.  No host synchronisation and no allocation per call: it can sit inside a captured loop.
+        The head is chosen by q.shape[-1]: 5 as above; 11 is the Minimized agents' (agents/Minimized: one Q per node, evg_step_vs_policy_minimized_q /
+        evg_step_vs_league_minimized_q), bit-identical to minimized_get_action(q, epsilon, seat) + step_vs(policy, rows, seat, features=...).  That head has
+        no directions (`directions=` raises ValueError): `actions_out` holds the rows {swarm, node}, which are both the orders and what SmartReplay records --
+        hand it the replay's slot_directions(t) view."""
         torch = _torch()
         league = policy if isinstance(policy, OpponentLeague) else None
         pid = None if league is not None else (self.POLICIES[policy] if isinstance(policy, str) else int(policy))
         N = self.num_envs
-        self._user(q, (N, _lib.NUM_GROUPS, 5), torch.float32, "q")
+        minimized = isinstance(q, torch.Tensor) and q.dim() == 3 and q.shape[-1] == _lib.MINI_QNET_OUT
+        if minimized and directions is not None:
+            raise ValueError("the Minimized head (q [N, 12, 11]) has no directions: actions_out holds the rows {swarm, node} the replay memory records")
+        self._user(q, (N, _lib.NUM_GROUPS, _lib.MINI_QNET_OUT if minimized else 5), torch.float32, "q")
         obs = self._seat_buffers() if out is None else self._user(out, (N, _lib.OBS_LEN), self.obs_dtype, "out")
         shared = swarm = None
         if features is not None:
@@ -280,6 +287,20 @@ class EvergladesVecEnv(object):
             eps_env = self._user(epsilon, (N,), torch.float32, "epsilon")
             epsilon = 0.0
         p = self._p
+        if minimized:
+            if league is not None:
+                rc = self.L.evg_step_vs_league_minimized_q(self._h, C.c_void_p(q.data_ptr()), float(epsilon), self._ptr(eps_env), self._league(league, seat),
+                                                           C.c_void_p(obs.data_ptr()), self._ptr(shared), self._ptr(swarm), self._ptr(actions_out),
+                                                           self._ptr(explored), p["reward"], p["done"], p["winner"], p["scores"], p["status"],
+                                                           self._stream())
+            else:
+                rc = self.L.evg_step_vs_policy_minimized_q(self._h, int(seat), C.c_void_p(q.data_ptr()), float(epsilon), self._ptr(eps_env), pid,
+                                                           C.c_void_p(obs.data_ptr()), self._ptr(shared), self._ptr(swarm), self._ptr(actions_out),
+                                                           self._ptr(explored), p["reward"], p["done"], p["winner"], p["scores"], p["status"],
+                                                           self._stream())
+            if rc:
+                self._check(rc)
+            return obs, self.reward, self.done, self._info
         if league is not None:               # a per-env bot (evg_step_vs_league_q): the caller's seat is the league's
             rc = self.L.evg_step_vs_league_q(self._h, C.c_void_p(q.data_ptr()), float(epsilon), self._ptr(eps_env), self._league(league, seat),
                                              C.c_void_p(obs.data_ptr()), self._ptr(shared), self._ptr(swarm), self._ptr(actions_out),
@@ -500,6 +521,39 @@ class EvergladesVecEnv(object):
         if rc:
             self._check(rc)
         return out
+
+    def minimized_get_action(self, q, epsilon, seat=0, out=None, explored=None):
+        """The Minimized agents' DQNAgent.get_action on the device (evg_minimized_get_action; agents/Minimized/DQNAgent.py:121-242): `q` float32 [N, 12, 11],
+        the network's output for every swarm, one Q per node.  Per env the epsilon coin, then get_random_actions (7 distinct swarms, 7 distinct nodes) or
+        get_best_actions (every swarm's {swarm, argmax + 1}, the seven with the LOWEST best Q in ascending stable order).  The agent reads no observation.
+        `epsilon`: a float in [0, 1] for every env, or a float32 tensor [N]; `seat` keys the draws; `explored`: a uint8 tensor [N] that receives 1 where the
+        random branch ran.  Returns int32 [N, 7, 2] {swarm, node}: what step_vs() takes as `actions` and SmartReplay as `directions`."""
+        torch = _torch()
+        N = self.num_envs
+        self._user(q, (N, _lib.NUM_GROUPS, _lib.MINI_QNET_OUT), torch.float32, "q")
+        if out is None:
+            self._seat_buffers()
+            out = self._actions_seat
+        self._user(out, (N, _lib.NUM_ACTIONS, 2), self._int32, "out")
+        if explored is not None:
+            self._user(explored, (N,), torch.uint8, "explored")
+        eps_env = None
+        if isinstance(epsilon, torch.Tensor):
+            eps_env = self._user(epsilon, (N,), torch.float32, "epsilon")
+            epsilon = 0.0
+        rc = self.L.evg_minimized_get_action(self._h, C.c_void_p(q.data_ptr()), float(epsilon), self._ptr(eps_env), int(seat), C.c_void_p(out.data_ptr()),
+                                             self._ptr(explored), self._stream())
+        if rc:
+            self._check(rc)
+        return out
+
+    def minimized_qnet(self, net, final_relu=None):
+        """The Minimized agents' Q network's forward pass on this env's device, one launch per call (everglades_amd.MinimizedQNet, evg_minimized_qnet):
+        `net` is the reference's QNetwork(59, 11, fc1) (fc1 / fc2, final ReLU), an nn.Sequential Linear(59, h)/ReLU/Linear(h, 11)[/ReLU], a 4-tuple
+        (w1, b1, w2, b2) with final_relu, or a pair of these (the two-seat layout); h in 1..128.  Its parameters are read in place on every call; the
+        output has no autograd."""
+        from .qnet import MinimizedQNet
+        return MinimizedQNet(self, net, final_relu=final_relu)
 
     def smart_replay(self, capacity_turns, n_step=1, gamma=0.999, shaping="normalized_score", seats=0, episode_base=0):
         """The Smart_State learner's n-step replay memory on the device for this env (everglades_amd.SmartReplay: Multi_Step.NStepModule +

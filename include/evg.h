@@ -41,7 +41,9 @@ extern "C" {
  *    evg_step_smart_q (the self-play turn: both seats' Q values decoded inside one step launch; an added function, no layout changed);
  *    evg_smart_qnet with its descriptor evg_qnet: the Smart_State Q network's forward pass in one launch (added, no layout changed);
  *    the opponent league: evg_league_clear / evg_league_assign / evg_league_importance / evg_step_vs_league / evg_step_vs_league_q with their descriptor
- *    evg_league -- added, no layout changed */
+ *    evg_league -- added, no layout changed;
+ *    the Minimized agents (agents/Minimized: a 59-h1-11 network, one Q per node): evg_minimized_get_action, evg_step_vs_policy_minimized_q,
+ *    evg_step_vs_league_minimized_q, evg_minimized_qnet with its descriptor evg_mini_qnet -- added, no layout changed */
 /* 6: evg_smart_get_action (DQNAgent.get_action with epsilon > 0), evg_step_vs_policy_smart (the learner-seat turn that also writes the Smart_State
  *    features), evg_get_run_state / evg_set_run_state (agent objects, returns, win counters: checkpoint / resume); reward / score buffers need 8-byte
  *    alignment only (5 asked 16 of every buffer)
@@ -715,6 +717,56 @@ EVG_API int evg_step_vs_league_q(evg_handle* h, const float* q, float epsilon, c
                                  void* obs_seat_out, float* shared_out, float* swarm_out,
                                  int32_t* actions_out, int32_t* directions_out, uint8_t* explored_out,
                                  float* reward_out, uint8_t* done_out, int8_t* winner_out, int32_t* scores_out, uint8_t* status_out, void* stream);
+
+/* ---- The Minimized agents (agents/Minimized: dqn_training, dqn_cycled_training(_with_importance), dqn_self_play, dqn_self_royale; Minimized_Rainbow) ----
+ * Their input is the Smart_State feature vector (create_swarm_obs, DQNAgent.py:244-276: evg_smart_state_compact and the fused feature stores serve it) and
+ * their n-step memory is the Smart_State one (the rows {swarm, node} below are what evg_replay_record takes as `directions`: action = node - 1).  What
+ * differs is the head: the network output is 11 wide, one Q per NODE, and swarm_think (:215-242) orders {swarm, argmax + 1} -- no Move_Translation, no
+ * location lookup, no observation.  Added under ABI 7: new functions and one new descriptor struct; nothing that existed changed.
+ *
+ * DECODE (q [N][12][11] float32, 16-byte aligned).  Per swarm: the FIRST maximum of its 11 values, a NaN is the maximum (torch.argmax / torch.max);
+ * node = argmax + 1 in the caller's own numbering; sort key = the maximum, a NaN key counts as +inf.  Greedy rows (get_best_actions, :155-178): the swarms
+ * sorted by key, ascending and stable; the first seven give rows {swarm, node}.  Exploration (get_action, :121-139; get_random_actions, :141-153) on the
+ * two keyed Philox blocks of the Smart_State agent call (domain 4, key (env id, episode, turn, seat), blocks 0 and 1, halves h0[0..7], h1[0..7]; a seat
+ * runs one agent family per turn): coin = (h0[7] << 16 | h1[7]) / 2^32 < epsilon in float64; swarms = partial Fisher-Yates over 0..11 with h0[0..6]
+ * (j = i + ((h0[i] * (12 - i)) >> 16), swap); nodes = partial Fisher-Yates over the pool 0..10 with h1[0..6] (j = i + ((h1[i] * (11 - i)) >> 16), swap,
+ * node_i = pool[i] + 1): np.random.choice(12, 7, replace=False) and np.random.choice(11, 7, replace=False) + 1.  The turn is the handle's.
+ *
+ * evg_minimized_get_action: DQNAgent.get_action for every env of the handle.  epsilon / epsilon_env as in evg_smart_get_action; epsilon == 0 with
+ * epsilon_env == NULL is get_best_actions.  actions_out int32 [N][7][2] {swarm, node}; explored_out uint8 [N] or NULL. */
+EVG_API int evg_minimized_get_action(evg_handle* h, const float* q, float epsilon, const float* epsilon_env, int seat, int32_t* actions_out,
+                                     uint8_t* explored_out, void* stream);
+/* The learner's turn from its Q values in one launch: evg_step_vs_policy_smart_q / evg_step_vs_league_q with the 11-way head -- their argument lists
+ * without directions_out (actions_out is both the orders and what the replay memory records), q [N][12][11]; shared_out / swarm_out optional (both NULL or
+ * both set, 16-byte aligned) and the same compact features.  Argument checks, error codes, alignment rules and launch as in those two.  Results -- every
+ * output, and afterwards the handle's state and run state (league: assign, objects, counts) -- are bit for bit those of evg_minimized_get_action followed
+ * by evg_step_vs_policy_smart / evg_step_vs_league with its rows.  Keyed-Philox handles only. */
+EVG_API int evg_step_vs_policy_minimized_q(evg_handle* h, int seat, const float* q, float epsilon, const float* epsilon_env, int opponent_policy,
+                                           void* obs_seat_out, float* shared_out, float* swarm_out, int32_t* actions_out, uint8_t* explored_out,
+                                           float* reward_out, uint8_t* done_out, int8_t* winner_out, int32_t* scores_out, uint8_t* status_out, void* stream);
+EVG_API int evg_step_vs_league_minimized_q(evg_handle* h, const float* q, float epsilon, const float* epsilon_env, const evg_league* lg,
+                                           void* obs_seat_out, float* shared_out, float* swarm_out, int32_t* actions_out, uint8_t* explored_out,
+                                           float* reward_out, uint8_t* done_out, int8_t* winner_out, int32_t* scores_out, uint8_t* status_out, void* stream);
+/* The Minimized Q network, inference only (agents/Minimized/QNetwork.py: relu(fc2(relu(fc1(x)))), 59 -> h1 -> 11): evg_smart_qnet's contract -- weights
+ * read in place on every call, the fmaf chain acc = b[j], fmaf(W[j][k], x[k], acc) for k ascending, fmaxf(acc, 0) on the hidden layer and (final_relu: the
+ * reference applies it) on the output, the compact prefix and one-hot term -- with two layers:
+ *   set p:   w1[p] [h1][59], b1[p] [h1], w2[p] [11][h1], b2[p] [11]           h1 in 1..128 (fc1_size of the reference's pickles; default 80)
+ * Layouts and row limits as evg_smart_qnet, q_out [R][12][11], [R][2][12][11] or [R][11].  Refused with EVG_ERR_INVALID (nothing launched):
+ * struct_size != sizeof(evg_mini_qnet), h1 outside 1..128, final_relu not 0/1, an unknown layout, a num_sets the layout does not take, a NULL or not
+ * 16-byte aligned pointer, R outside 1..2^30. */
+#define EVG_MINI_QNET_MAX_HIDDEN 128
+typedef struct evg_mini_qnet {
+    uint32_t struct_size;          /* sizeof(evg_mini_qnet)                                        */
+    int32_t h1;                    /* hidden size, 1..128                                          */
+    int32_t final_relu;            /* 0 / 1: fmaxf(q, 0) on the output layer                       */
+    int32_t num_sets;              /* 1, or 2 for EVG_QNET_COMPACT_SEATS                           */
+    const float* w1[2];
+    const float* b1[2];
+    const float* w2[2];
+    const float* b2[2];
+} evg_mini_qnet;
+EVG_API int evg_minimized_qnet(evg_handle* h, const evg_mini_qnet* net, int layout, int64_t rows, const float* in0, const float* in1, float* q_out,
+                               void* stream);
 
 #ifdef __cplusplus
 }

@@ -54,12 +54,16 @@ STEP_FORMS = {"single_turn": (64, 0, 0, 0, 0, 1, 0, 0), "persistent": (64, 1, 0,
               "two_seat_q": (64, 0, 0, 0, 0, 1, 1, 0), "seat_league": (64, 0, 0, 0, 1, 1, 0, 1), "seat_q_league": (64, 0, 0, 0, 1, 1, 1, 1),
               # diagnostic libraries only
               "helper_lanes": (32, 0, 0, 0, 0, 1, 0, 0), "helper_lanes_persistent": (32, 1, 0, 0, 0, 1, 0, 0), "wg256": (64, 0, 0, 0, 0, 4, 0, 0)}
+# evg_step_minimized_kernel<OT, LEAGUE> (SeatQMin, SeatQMinLeague): the one-seat Q form's body with the 11-way head
+MINIMIZED_FORMS = {"seat_q_min": 0, "seat_q_min_league": 1}
 OBS_MANGLED = {"float32": "f", "float64": "d", "int16": "s"}
 
 
 def step_kernel_symbol(form, obs_dtype="float32"):
     """the mangled symbol of a step-kernel form (a key of STEP_FORMS) for an observation type: what nm, the device assembly and the compiler's
     resource-usage remarks call it"""
+    if form in MINIMIZED_FORMS:       # the one-seat Q form with the Minimized agents' 11-way head: a kernel of its own name, <OT, LEAGUE>
+        return "_ZN3evg25evg_step_minimized_kernelI%sLb%dEEEvNS_8StepArgsE" % (OBS_MANGLED[obs_dtype], MINIMIZED_FORMS[form])
     lpw, multi, mt, chunked, seat, wpb, qdec, league = STEP_FORMS[form]
     return "_ZN3evg15evg_step_kernelI%sLi%dELb%dELb%dELb%dELb%dELi%dELb%dELb%dEEEvNS_8StepArgsE" % (OBS_MANGLED[obs_dtype], lpw, multi, mt, chunked, seat, wpb,
                                                                                                          qdec, league)
