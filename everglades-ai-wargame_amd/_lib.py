@@ -31,6 +31,7 @@ EXPORTS = ["evg_default_tables", "evg_create", "evg_destroy", "evg_reset", "evg_
            "evg_replay_gather", "evg_smart_qnet",
            "evg_league_clear", "evg_league_assign", "evg_league_importance", "evg_step_vs_league", "evg_step_vs_league_q",
            "evg_minimized_get_action", "evg_step_vs_policy_minimized_q", "evg_step_vs_league_minimized_q", "evg_minimized_qnet",
+           "evg_step_minimized_q", "evg_step_league_minimized_q",
            "evg_observe_seat",
            "evg_random_actions_seat", "evg_smart_state_seat", "evg_smart_state_compact", "evg_check_fault", "evg_rollout_vs_policy", "evg_fog_of_war",
            "evg_sightings", "evg_smart_state", "evg_smart_actions", "evg_smart_get_action", "evg_move_table", "evg_random_actions", "evg_rollout_random", "evg_rollout_policies",
@@ -229,6 +230,8 @@ def load(path=None):
     L.evg_minimized_get_action.argtypes = [vp, vp, C.c_float, vp, C.c_int, vp, vp, vp]
     L.evg_step_vs_policy_minimized_q.argtypes = [vp, C.c_int, vp, C.c_float, vp, C.c_int, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]
     L.evg_step_vs_league_minimized_q.argtypes = [vp, vp, C.c_float, vp, lp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]
+    L.evg_step_minimized_q.argtypes = [vp, vp, C.c_float, C.c_float, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]
+    L.evg_step_league_minimized_q.argtypes = [vp, vp, C.c_float, C.c_float, vp, lp, C.c_int, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]
     L.evg_minimized_qnet.argtypes = [vp, C.POINTER(EvgMiniQnet), C.c_int, C.c_int64, vp, vp, vp, vp]
     L.evg_random_actions_seat.argtypes = [vp, C.c_int, vp, vp]
     L.evg_smart_state_seat.argtypes = [vp, vp, vp, vp]

@@ -194,9 +194,9 @@ static int check_fault(evg_handle* h, uint32_t* word_out = nullptr) {
 // The key of the graph cache: every field of StepIO that the caller owns (the launcher-owned ones -- env_lo, env_hi, flags, nsets, chunk_turns, grid_slots,
 // progress_base -- are set by launch_step inside the captured plan).  A new field of StepIO changes its size: visit same_launch, then the number.
 #ifdef EVG_DIAG
-static_assert(sizeof(StepIO) == 256, "StepIO changed (diagnostic layout): visit same_launch");
+static_assert(sizeof(StepIO) == 264, "StepIO changed (diagnostic layout): visit same_launch");
 #else
-static_assert(sizeof(StepIO) == 240, "StepIO changed: visit same_launch");
+static_assert(sizeof(StepIO) == 248, "StepIO changed: visit same_launch");
 #endif
 static bool same_launch(const StepIO& a, const StepIO& b) {
     bool same = a.actions == b.actions && a.obs == b.obs && a.reward == b.reward && a.done == b.done && a.winner == b.winner && a.scores == b.scores &&
@@ -205,7 +205,8 @@ static bool same_launch(const StepIO& a, const StepIO& b) {
                 a.feat_shared == b.feat_shared && a.feat_swarm == b.feat_swarm && a.q == b.q && a.eps == b.eps && a.eps1 == b.eps1 &&
                 a.eps_env == b.eps_env && a.q_actions == b.q_actions && a.q_directions == b.q_directions && a.q_explored == b.q_explored &&
                 a.lg_weights == b.lg_weights && a.lg_assign == b.lg_assign && a.lg_objects == b.lg_objects && a.lg_counts == b.lg_counts &&
-                a.lg_ctl == b.lg_ctl && a.lg_members == b.lg_members && a.lg_num == b.lg_num && a.lg_resample == b.lg_resample;
+                a.lg_ctl == b.lg_ctl && a.lg_members == b.lg_members && a.lg_num == b.lg_num && a.lg_resample == b.lg_resample &&
+                a.lg_qmember == b.lg_qmember;
 #ifdef EVG_DIAG
     same = same && a.lanes_per_wave == b.lanes_per_wave && a.ablate == b.ablate && a.stamps == b.stamps;
 #endif
@@ -1119,6 +1120,62 @@ int evg_step_vs_league_minimized_q(evg_handle* h, const float* q, float epsilon,
     io.q = q; io.eps = epsilon; io.eps_env = epsilon_env;
     io.q_actions = actions_out; io.q_explored = explored_out;
     return launched("step", launch_step_minimized(h->S, io, h->cfg.obs_dtype, h->caps, stream));
+} catch (...) { return on_exception(); }
+
+// the two-seat forms: Minimized self-play in one launch (q [N][2][12][11]; both seats' observations, features, rows and explore flags)
+static int check_two_seat_minimized(const evg_handle* h, const float* q, float epsilon0, float epsilon1, const float* epsilon_env, void* obs_out,
+                                    float* shared_out, float* swarm_out, int32_t* actions_out, float* reward_out, uint8_t* done_out, int32_t* scores_out) {
+    if (!q || !obs_out || !reward_out || !done_out) return fail(EVG_ERR_INVALID, "q, obs_out, reward_out and done_out are required");
+    if (!epsilon_env && !(epsilon0 >= 0.0f && epsilon0 <= 1.0f && epsilon1 >= 0.0f && epsilon1 <= 1.0f))
+        return fail(EVG_ERR_INVALID, "epsilon0 %g / epsilon1 %g outside [0, 1]", (double)epsilon0, (double)epsilon1);
+    if (const int rc = check_feature_pair(shared_out, swarm_out)) return rc;
+    // (the fused feature store writes shared_out and swarm_out as float4)
+    EVG_NEED_ALIGNED16(q); EVG_NEED_ALIGNED16(obs_out); EVG_NEED_ALIGNED16(shared_out); EVG_NEED_ALIGNED16(swarm_out);
+    EVG_NEED_ALIGNED16(actions_out); EVG_NEED_ALIGNED8(reward_out); EVG_NEED_ALIGNED8(scores_out);
+    (void)h;
+    return EVG_OK;
+}
+
+int evg_step_minimized_q(evg_handle* h, const float* q, float epsilon0, float epsilon1, const float* epsilon_env, void* obs_out, float* shared_out,
+                         float* swarm_out, int32_t* actions_out, uint8_t* explored_out, float* reward_out, uint8_t* done_out, int8_t* winner_out,
+                         int32_t* scores_out, uint8_t* status_out, void* stream) try {
+    if (!h) return fail(EVG_ERR_INVALID, "null handle");
+    if (const int rc = check_two_seat_minimized(h, q, epsilon0, epsilon1, epsilon_env, obs_out, shared_out, swarm_out, actions_out, reward_out, done_out,
+                                                scores_out))
+        return rc;
+    if (const int rc = check_keyed_philox(h, "evg_step_minimized_q", " (the stock-entropy mode has no fused decode)")) return rc;
+    EVG_ON_DEVICE(h);
+    LaunchIO io(h);
+    io.obs = obs_out;
+    io.reward = reward_out; io.done = done_out; io.winner = winner_out; io.scores = scores_out; io.status = status_out;
+    io.feat_shared = shared_out; io.feat_swarm = swarm_out;
+    io.q = q; io.eps = epsilon0; io.eps1 = epsilon1; io.eps_env = epsilon_env;
+    io.q_actions = actions_out; io.q_explored = explored_out;
+    io.lg_qmember = -1;
+    return launched("step", launch_step_minimized2(h->S, io, h->cfg.obs_dtype, h->caps, stream));
+} catch (...) { return on_exception(); }
+
+int evg_step_league_minimized_q(evg_handle* h, const float* q, float epsilon0, float epsilon1, const float* epsilon_env, const evg_league* lg, int q_member,
+                                void* obs_out, float* shared_out, float* swarm_out, int32_t* actions_out, uint8_t* explored_out, float* reward_out,
+                                uint8_t* done_out, int8_t* winner_out, int32_t* scores_out, uint8_t* status_out, void* stream) try {
+    if (!h) return fail(EVG_ERR_INVALID, "null handle");
+    if (const int rc = check_two_seat_minimized(h, q, epsilon0, epsilon1, epsilon_env, obs_out, shared_out, swarm_out, actions_out, reward_out, done_out,
+                                                scores_out))
+        return rc;
+    { const int rc = check_league(h, lg); if (rc) return rc; }
+    if (q_member < -1 || q_member >= lg->num_members)
+        return fail(EVG_ERR_ARG, "league: q_member must be -1 (no network member) or lie in 0..%d (got %d)", lg->num_members - 1, q_member);
+    EVG_ON_DEVICE(h);
+    LaunchIO io(h);
+    io.obs = obs_out;
+    io.reward = reward_out; io.done = done_out; io.winner = winner_out; io.scores = scores_out; io.status = status_out;
+    league_io(io, lg);
+    io.feat_shared = shared_out; io.feat_swarm = swarm_out;
+    io.q = q; io.eps = epsilon0; io.eps1 = epsilon1; io.eps_env = epsilon_env;
+    // the rows PLAYED: the league seat's are its bot's where a bot plays, so they leave with the orders (step_orders.inc), not with the decode
+    io.actions_out = actions_out; io.q_explored = explored_out;
+    io.lg_qmember = q_member;
+    return launched("step", launch_step_minimized2(h->S, io, h->cfg.obs_dtype, h->caps, stream));
 } catch (...) { return on_exception(); }
 
 int evg_minimized_qnet(evg_handle* h, const evg_mini_qnet* net, int layout, int64_t rows, const float* in0, const float* in1, float* q_out, void* stream) try {

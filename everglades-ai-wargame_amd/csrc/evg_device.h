@@ -173,6 +173,9 @@ struct StepIO {
     uint32_t  ablate;            // bit0 orders, bit1 combat, bit2 movement, bit4 obs write-out, bit5 state store
     unsigned long long* stamps;  // EVG_STAMPS only, else NULL
 #endif
+    // two-seat league form (evg_step_league_minimized_q): the member whose league-seat rows are decoded from io.q instead of drawn from its bot, -1: none.
+    // (behind every older field, in both layouts: the kernels there were read their arguments at the offsets they always did)
+    int32_t   lg_qmember;
 };
 
 constexpr int32_t STEP_F_STAGGER = 1;      // single-turn launch whose whole grid is resident at once: the wave in hardware slot 1 of a SIMD starts late
@@ -239,6 +242,7 @@ int launch_replay_gather(const DevState& S, const evg_replay& m, int batch, cons
 int launch_smart_qnet(const evg_qnet& net, int layout, long long rows, const float* in0, const float* in1, float* q_out, int num_cu, void* stream);
 // the Minimized agents' decode and Q network (minimized_decode.inc, minimized_qnet.inc); arguments validated by the caller (evg_abi.hip)
 int launch_step_minimized(const DevState& S, const StepIO& io, int obs_dtype, const DeviceCaps& caps, void* stream);
+int launch_step_minimized2(const DevState& S, const StepIO& io, int obs_dtype, const DeviceCaps& caps, void* stream);
 int launch_minimized_actions(const DevState& S, const float* q, int32_t* actions, void* stream, const SmartExplore* explore /* NULL: get_best_actions only */,
                              uint8_t* explored /* device [N] or NULL */);
 int launch_minimized_qnet(const evg_mini_qnet& net, int layout, long long rows, const float* in0, const float* in1, float* q_out, int num_cu, void* stream);

@@ -118,16 +118,19 @@ struct SeatLeague : Seat { static constexpr bool league = true; };
 struct SeatQLeague : SeatQ { static constexpr bool league = true; };
 struct SeatQMin : SeatQ { static constexpr int head = HEAD_MINIMIZED; };
 struct SeatQMinLeague : SeatQMin { static constexpr bool league = true; };
+struct TwoSeatQMin : TwoSeatQ { static constexpr int head = HEAD_MINIMIZED; };
+struct TwoSeatQMinLeague : TwoSeatQMin { static constexpr bool league = true; };
 #ifdef EVG_DIAG
 // diagnostic library, lanes = 32: 16 envs per wavefront + 32 helper lanes, in both launch forms
 template <typename Form> struct HelperLanes : Form { static constexpr int lanes = WG / 2; };
 struct Wg256 : SingleTurn { static constexpr int waves_per_block = 4; };
 #endif
 // (OT, form) -> the kernel, e.g. SeatQ with float32 observations: evg_step_kernel<float, 64, false, false, false, true, 1, true, false>
-// (the 11-way head: evg_step_minimized_kernel<OT, LEAGUE>, a kernel of its own name -- step_kernel.inc)
+// (the 11-way head: evg_step_minimized_kernel<OT, LEAGUE>, two seats evg_step_minimized2_kernel<OT, LEAGUE>: kernels of their own names -- step_kernel.inc)
 template <typename OT, typename Form>
 constexpr auto step_kernel_of_head() {
-    if constexpr (Form::head == HEAD_MINIMIZED) return evg_step_minimized_kernel<OT, Form::league>;
+    if constexpr (Form::head == HEAD_MINIMIZED && !Form::seat) return evg_step_minimized2_kernel<OT, Form::league>;
+    else if constexpr (Form::head == HEAD_MINIMIZED) return evg_step_minimized_kernel<OT, Form::league>;
     else return evg_step_kernel<OT, Form::lanes, Form::multi, Form::stock_mt, Form::chunked, Form::seat, Form::waves_per_block, Form::qdec, Form::league>;
 }
 template <typename OT, typename Form>
@@ -443,6 +446,14 @@ int launch_step_minimized(const DevState& S, const StepIO& io_in, int obs_dtype,
     if (S.mt_key || !io_in.q) return -1;
     const StepIO io = single_turn_io(S, io_in, caps);
     return io.lg_assign ? launch_form<SeatQMinLeague>(S, io, obs_dtype, s) : launch_form<SeatQMin>(S, io, obs_dtype, s);
+}
+
+// evg_step_minimized_q / evg_step_league_minimized_q: the two-seat Q form with the 11-way head (io.lg_assign: its league form)
+int launch_step_minimized2(const DevState& S, const StepIO& io_in, int obs_dtype, const DeviceCaps& caps, void* stream) {
+    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+    if (S.mt_key || !io_in.q) return -1;
+    const StepIO io = single_turn_io(S, io_in, caps);
+    return io.lg_assign ? launch_form<TwoSeatQMinLeague>(S, io, obs_dtype, s) : launch_form<TwoSeatQMin>(S, io, obs_dtype, s);
 }
 
 // the Minimized agents' network output -> orders: one DPP row (16 lanes) per env; ex NULL: get_best_actions only

@@ -59,3 +59,17 @@ __global__ void __launch_bounds__(WG) __attribute__((amdgpu_waves_per_eu(2, 2)))
     constexpr bool MULTI = false, MT = false, CHUNKED = false, SEAT = true, QDEC = true;
 #include "step_kernel_body.inc"
 }
+
+// the TWO-seat Q form with the 11-way head (evg_step_minimized_q, TwoSeatQMin: Minimized self-play, a DQNAgent on each seat): the !SEAT skeleton of the Q
+// prologue -- seat 0, then seat 1 through the same LDS rows, each lane drawing both Philox blocks of its own seat's agent call -- with the decode reading
+// seat p's [12][11] block of io.q [N][2][12][11]; both players' observations and features as evg_step_smart_q.
+// LEAGUE (evg_step_league_minimized_q, TwoSeatQMinLeague): the seat 1 - io.seat is the league's, and ONE member -- io.lg_qmember, -1: none -- is the
+// caller's second network instead of a bot: where assign[e] is that member the league seat's rows are the decode of q[e][1 - seat], elsewhere the member's
+// bot plays (agent_rows) and the second decode pass skips the env.  Assignment, tally, redraw and object swap are the one-seat league forms'.
+// A kernel of its own name: every instantiation of the two kernels above keeps its mangled name and its instruction stream.
+template <typename OT, bool LEAGUE>
+__global__ void __launch_bounds__(WG) __attribute__((amdgpu_waves_per_eu(2, 2))) evg_step_minimized2_kernel(StepArgs) {
+    constexpr int LPW = WG, WPB = 1, HEAD = HEAD_MINIMIZED;
+    constexpr bool MULTI = false, MT = false, CHUNKED = false, SEAT = false, QDEC = true;
+#include "step_kernel_body.inc"
+}

@@ -1,12 +1,16 @@
-// step_kernel_body.inc -- the body of the step kernel: a textual fragment of evg_step_kernel and evg_step_minimized_kernel (step_kernel.inc, which
-// documents the forms), compiled with the names OT, LPW, MULTI, MT, CHUNKED, SEAT, WPB, QDEC, LEAGUE and HEAD in scope.
-    static_assert(HEAD == HEAD_SMART || (QDEC && SEAT), "the 11-way head exists in the one-seat Q forms only");
+// step_kernel_body.inc -- the body of the step kernel: a textual fragment of evg_step_kernel, evg_step_minimized_kernel and evg_step_minimized2_kernel
+// (step_kernel.inc, which documents the forms), compiled with the names OT, LPW, MULTI, MT, CHUNKED, SEAT, WPB, QDEC, LEAGUE and HEAD in scope.
+    static_assert(HEAD == HEAD_SMART || QDEC, "the 11-way head exists in the Q forms only (one seat or two)");
     static_assert(!MT || (!MULTI && LPW == WG), "the stock-entropy mode exists in the single-turn, 32-envs-per-wave form only");
     static_assert(!CHUNKED || (MULTI && LPW == WG && !MT), "the chunked form is an instantiation of the persistent two-lane kernel");
     static_assert(!SEAT || (!MULTI && !MT && LPW == WG), "the one-seat form is an instantiation of the single-turn two-lane kernel");
     static_assert(WPB == 1 || (!MULTI && !MT && !CHUNKED && !SEAT && LPW == WG), "several wavefronts per workgroup: the plain single-turn two-lane form only");
     static_assert(!QDEC || (!MULTI && !MT && LPW == WG && WPB == 1), "the Q form is an instantiation of the single-turn two-lane kernel (one seat or two)");
-    static_assert(!LEAGUE || SEAT, "the league forms are instantiations of the one-seat kernel (with or without the Q decode)");
+    static_assert(!LEAGUE || SEAT || (QDEC && HEAD == HEAD_MINIMIZED),
+                  "the league forms are instantiations of the one-seat kernel (with or without the Q decode) or of the two-seat 11-way Q form");
+    // the two-seat 11-way forms decode their orders or take them from the league's bots: io.gen_actions is 0 or 2 there, never 1 (orders drawn in the
+    // kernel), and the tests for 1 -- a wave-wide condition the compiler otherwise keeps in scalar registers across the turn -- are compiled out
+    constexpr bool DRAWS_ORDERS = !(QDEC && !SEAT && HEAD == HEAD_MINIMIZED);
     step_args_ptr A = (step_args_ptr)__builtin_amdgcn_kernarg_segment_ptr();
     constexpr int EPW = LPW / 2;                        // envs per wavefront
     constexpr int DP_CAP = CombatLds<LPW>::DP_CAP;
@@ -58,7 +62,11 @@
         wg_set = (q - wg_chunk * q_nx) * S.nxcd + q_xi;
     }
     const int e0 = io.env_lo + wg_set * EPW;          // this launch plays envs [env_lo, env_hi) of the handle (launch_step)
-    const int nvalid = min(EPW, io.env_hi - e0);
+    int nvalid_ = min(EPW, io.env_hi - e0);
+    // (two-seat league form: opaque, so that `nvalid == EPW` at the turn's end is a test of this register -- the compiler otherwise tests env_hi - e0, keeps
+    // that in a scalar register of its own across the whole turn and, in that form alone, spills it)
+    if constexpr (LEAGUE && !SEAT) asm volatile("" : "+s"(nvalid_));
+    const int nvalid = nvalid_;
     const bool valid = envlane && E < nvalid;
     const int e = valid ? e0 + E : e0;
     const size_t N = (size_t)S.N;
@@ -147,8 +155,9 @@
     if constexpr (QDEC) {
         static_assert(NG * 5 % 4 == 0, "an env's Q values are a whole number of 16-byte pieces");
         [[maybe_unused]] const int nq = nvalid * (NG * 5 / 4);
-        if constexpr (HEAD == HEAD_MINIMIZED) {
-            eps_q = io.eps_env ? io.eps_env[e] : io.eps;                       // (the 11-way head's values are read by the decode itself)
+        if constexpr (HEAD == HEAD_MINIMIZED) {                                // (the 11-way head's values are read by the decode itself)
+            if constexpr (SEAT) eps_q = io.eps_env ? io.eps_env[e] : io.eps;
+            else eps_q = io.eps_env ? io.eps_env[(size_t)e * 2 + P] : (P ? io.eps1 : io.eps);
         } else if constexpr (SEAT) {
             const uint4* qs = reinterpret_cast<const uint4*>(io.q) + (size_t)e0 * (NG * 5 / 4);      // 16-byte aligned (checked by the entry point)
 #pragma unroll
@@ -199,7 +208,7 @@
         }
         // ... and the orders this kernel draws itself need only the turn and the episode (the first two loads), so they are
         // drawn while the group / node words are still on their way
-        if (io.gen_actions == 1) gen_random_rows(S.seed_lo, S.seed_hi, S.env_id_base + (uint32_t)e, episode, turn, P, act_in);
+        if (DRAWS_ORDERS && io.gen_actions == 1) gen_random_rows(S.seed_lo, S.seed_hi, S.env_id_base + (uint32_t)e, episode, turn, P, act_in);
         if constexpr (QDEC) {
             // the caller's agent call draws two Philox blocks (smart_decode.inc): each lane of the pair draws one -- block P -- and the pair swaps them
             // (DPP), so that both lanes hold the env's coin and draws, no lane idles behind its partner
@@ -210,8 +219,10 @@
                 if constexpr (HEAD == HEAD_MINIMIZED) qdraw = minimized_explore_words(P ? o : b, P ? b : o, eps_q);
                 else qdraw = smart_explore_words(P ? o : b, P ? b : o, eps_q);
             } else {
-                qdraw = smart_explore_words(rng_block(S.seed_lo, S.seed_hi, S.env_id_base + (uint32_t)e, episode, RNG_EXPLORE, 0u, turn, 0, P, 0),
-                                            rng_block(S.seed_lo, S.seed_hi, S.env_id_base + (uint32_t)e, episode, RNG_EXPLORE, 1u, turn, 0, P, 0), eps_q);
+                const uint4 b0 = rng_block(S.seed_lo, S.seed_hi, S.env_id_base + (uint32_t)e, episode, RNG_EXPLORE, 0u, turn, 0, P, 0);
+                const uint4 b1 = rng_block(S.seed_lo, S.seed_hi, S.env_id_base + (uint32_t)e, episode, RNG_EXPLORE, 1u, turn, 0, P, 0);
+                if constexpr (HEAD == HEAD_MINIMIZED) qdraw = minimized_explore_words(b0, b1, eps_q);
+                else qdraw = smart_explore_words(b0, b1, eps_q);
             }
         }
     }
@@ -264,14 +275,21 @@
         // are decoded and written out, frozen ones included, as evg_smart_get_action writes every env.
         // (two-seat form: seat 0, then seat 1, each with its own numbering and its own draws)
         const int sw = lane & 15, sub = lane >> 4;
+        // two-seat league form: the envs whose league seat the NETWORK plays (member io.lg_qmember), bit 2 E; the league seat's pass decodes those only
+        [[maybe_unused]] uint64_t lg_qenvs = 0;
+        if constexpr (LEAGUE && !SEAT) lg_qenvs = __ballot(P == 0 && lg_m == io.lg_qmember);
         auto decode = [&](int seat) {
             if constexpr (HEAD == HEAD_MINIMIZED) {
                 // the 11-way head: {swarm, argmax + 1}, no location, no directions; envs beyond the launch's last read nothing
                 for (int ps = 0; ps < EPW / 4; ++ps) {
                     const int ep = 4 * ps + sub;          // env slot of this lane's row
-                    const bool live = ep < nvalid, act = sw < NG && live;
+                    bool live = ep < nvalid;
+                    if constexpr (LEAGUE && !SEAT) live = live && (seat == io.seat || ((lg_qenvs >> (2 * ep)) & 1ull));
+                    const bool act = sw < NG && live;
                     int node;
-                    const int rank = minimized_decide(io.q + (size_t)(e0 + (live ? ep : 0)) * (NG * MIN_Q), act, live, sw, L.u.sq.draws[ep], node);
+                    // (two-seat form: seat p's [12][11] block of env e is block 2 e + p)
+                    const size_t qblock = SEAT ? (size_t)(e0 + (live ? ep : 0)) : (size_t)(e0 + (live ? ep : 0)) * 2 + (size_t)seat;
+                    const int rank = minimized_decide(io.q + qblock * (NG * MIN_Q), act, live, sw, L.u.sq.draws[ep], node);
                     if (act && rank < NA) L.u.sq.rows[ep][rank] = make_int2(sw, node);
                 }
             } else {
@@ -323,11 +341,17 @@
 #pragma unroll
                     for (int i = 0; i < NA; ++i) act_in[i] = L.u.sq.rows[E][i];
                 }
+                // (two-seat league form: the rows PLAYED leave through io.actions_out in step_orders.inc -- the league seat's may be a bot's)
                 if (io.q_actions) put_rows2(io.q_actions, &L.u.sq.rows[0][0], s);
-                if (io.q_directions) put_rows2(io.q_directions, &L.u.sq.dirs[0][0], s);
+                if constexpr (HEAD == HEAD_SMART)
+                    if (io.q_directions) put_rows2(io.q_directions, &L.u.sq.dirs[0][0], s);
                 WAVE_SYNC();                              // the next seat's values, then the turn's scratch, replace this seat's rows
             }
-            if (valid && io.q_explored) io.q_explored[(size_t)e * 2 + P] = (uint8_t)(qdraw.x >> 31);
+            if constexpr (LEAGUE) {                       // 2: the league seat of an env whose member is a bot -- not a transition of the second network
+                if (valid && io.q_explored) io.q_explored[(size_t)e * 2 + P] = (P != io.seat && lg_m != io.lg_qmember) ? (uint8_t)2 : (uint8_t)(qdraw.x >> 31);
+            } else {
+                if (valid && io.q_explored) io.q_explored[(size_t)e * 2 + P] = (uint8_t)(qdraw.x >> 31);
+            }
         } else {
             decode(io.seat);
             if (P == io.seat) {

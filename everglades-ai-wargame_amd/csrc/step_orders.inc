@@ -5,7 +5,7 @@
     // here by the same generators as evg_random_actions / evg_scripted_actions and written out
     int2 act[NA];
     if (io.gen_actions) {
-        if (io.gen_actions == 1) {
+        if (DRAWS_ORDERS && io.gen_actions == 1) {
             if constexpr (MULTI) {
                 uint32_t rk[20];
 #pragma unroll
@@ -22,12 +22,15 @@
             int pol0 = io.policy0, pol1 = io.policy1;
             asm volatile("" : "+s"(pol0), "+s"(pol1));
             const AgentTabs atabs{L.tab.nib[11], L.tab.nib[12], L.tab.nib[13], T};
-            const bool bot_lane = !SEAT || P != io.seat;        // one-seat form: the caller's lane has no agent (its object is neither consulted nor stored)
+            bool bot_lane = !SEAT || P != io.seat;              // one-seat form: the caller's lane has no agent (its object is neither consulted nor stored)
+            // two-seat league form: only the league seat of an env whose member is a bot (member io.lg_qmember is the caller's second network: its rows
+            // were decoded in the prologue, its bot is never consulted and its object words stay as they are)
+            if constexpr (LEAGUE && !SEAT) bot_lane = P != io.seat && lg_m != io.lg_qmember;
             int pol = P ? pol1 : pol0;
             if constexpr (LEAGUE) pol = lg_pol;                 // a per-lane value: the env's member (the caller's lane is not a bot lane)
             agent_rows(pol, view, atabs, S.seed_lo, S.seed_hi, S.env_id_base + (uint32_t)e, episode, P, true, status == 0 && bot_lane,
                        &ag_cycle, &ag_swarm, &ag_dfs, act);
-            if constexpr (SEAT) {
+            if constexpr (SEAT || LEAGUE) {
 #pragma unroll
                 for (int i = 0; i < NA; ++i) act[i] = bot_lane ? act[i] : act_in[i];
             }
@@ -58,7 +61,7 @@
         // commanded this turn) and, for aliased ids, through the order of the writes (the later row wins, as in
         // the reference).  That makes the 7 LDS lookups independent instead of a 7-deep dependent chain.
         const uint64_t node_map = player_node_map(P, p1nib);
-        if (!ABLATED(1u) && io.gen_actions == 1) {
+        if (DRAWS_ORDERS && !ABLATED(1u) && io.gen_actions == 1) {
             // Orders drawn in this kernel by gen_random_rows: 7 DISTINCT group ids in 0..11 and node ids in 1..11 by construction, so
             // the domain checks, the Python-list negative indices and the "already commanded this turn" test of the general path
             // below cannot trigger; every row is independent.

@@ -6,6 +6,10 @@ and `updateAgentWeights` (:166-173) moves the weights towards the bots the learn
 `resample=False` with a caller-written assignment is evaluate_all.py's shape: one learner against every bot at once, a win rate per bot.
 
 The class owns the league's device tensors; `env.step_vs(league, ...)` / `env.step_vs_q(league, ...)` take it where they take a policy name.
+
+One member may be "q": the caller's SECOND network instead of a bot (agents/Minimized/training_scripts/dqn_staggered_self_play.py, where seat 1 is drawn
+once per episode from the second DQN or a scripted bot).  Such a league is played by `env.step_q(q [N, 2, 12, 11], ..., league=league)` only
+(evg_step_league_minimized_q), which decodes that member's rows from q[:, 1 - seat].
 """
 import ctypes as C
 
@@ -17,10 +21,16 @@ from . import _lib
 class OpponentLeague(object):
     def __init__(self, env, members, weights=None, seat=0, resample=True):
         """members: names from _lib.POLICY_NAMES (or their aliases) or EVG_POLICY_* ids, 1..16 of them; ids may repeat -- repeated ids are distinct
-        members with their own agent objects and counters.  weights: one float per member (default 1.0 each).  seat: the CALLER's seat; the league plays
+        members with their own agent objects and counters.  At most one member may be the string "q": the caller's second network (`q_member` is its
+        index, -1 without one; the descriptor holds EVG_POLICY_NO_ACTION for it, a bot that is never consulted).  weights: one float per member (default 1.0 each).  seat: the CALLER's seat; the league plays
         1 - seat.  The constructor ends with clear(): create the league after env.reset(), or call assign_after_reset() after it."""
         import torch
-        ids = [env.POLICIES[m] if isinstance(m, str) else int(m) for m in members]
+        members = list(members)
+        qs = [i for i, m in enumerate(members) if isinstance(m, str) and m == "q"]
+        if len(qs) > 1:
+            raise ValueError("a league has at most one \"q\" member (the caller's second network), got %d" % len(qs))
+        self.q_member = qs[0] if qs else -1
+        ids = [env.POLICIES["no_action"] if i == self.q_member else (env.POLICIES[m] if isinstance(m, str) else int(m)) for i, m in enumerate(members)]
         if not 1 <= len(ids) <= _lib.LEAGUE_MAX_MEMBERS:
             raise ValueError("a league has 1..%d members, got %d" % (_lib.LEAGUE_MAX_MEMBERS, len(ids)))
         if any(i < 0 or i >= len(_lib.POLICY_NAMES) for i in ids):

@@ -215,7 +215,7 @@ class EvergladesVecEnv(object):
         features=(shared [N, 34], swarm [N, 12, 13]) float32 tensors: the launch ALSO writes the Smart_State features of the new observation into them
         (evg_step_vs_policy_smart: what smart_state_compact(-1, obs_seat, shared, swarm) would compute afterwards, without that kernel)."""
         torch = _torch()
-        league = policy if isinstance(policy, OpponentLeague) else None
+        league = self._bot_league(policy)
         pid = None if league is not None else (self.POLICIES[policy] if isinstance(policy, str) else int(policy))
         a = actions
         if not (type(a) is torch.Tensor and a.dtype is self._int32 and a.device == self.device and a.is_contiguous()):
@@ -263,7 +263,7 @@ class EvergladesVecEnv(object):
         no directions (`directions=` raises ValueError): `actions_out` holds the rows {swarm, node}, which are both the orders and what SmartReplay records --
         hand it the replay's slot_directions(t) view."""
         torch = _torch()
-        league = policy if isinstance(policy, OpponentLeague) else None
+        league = self._bot_league(policy)
         pid = None if league is not None else (self.POLICIES[policy] if isinstance(policy, str) else int(policy))
         N = self.num_envs
         minimized = isinstance(q, torch.Tensor) and q.dim() == 3 and q.shape[-1] == _lib.MINI_QNET_OUT
@@ -317,17 +317,29 @@ class EvergladesVecEnv(object):
             self._check(rc)
         return obs, self.reward, self.done, self._info
 
-    def step_q(self, q, epsilon, features=None, directions=None, explored=None, actions_out=None, out=None):
+    def step_q(self, q, epsilon, features=None, directions=None, explored=None, actions_out=None, out=None, league=None):
         """The self-play turn from both seats' Q values, in ONE launch (evg_step_smart_q): DQNAgent.get_action for seat 0 and for seat 1 -- each its own
         epsilon coin, then get_random_actions or get_best_actions, as smart_get_action() -- then step() with both seats' rows.  `q` float32 [N, 2, 12, 5]: row
         [e, p] is seat p's network output; `epsilon` a float in [0, 1] for both seats, a pair (eps0, eps1), or a float32 tensor [N, 2].  Returns (obs [N, 2, 105],
         reward [N, 2], done [N], info) like step(); bit-identical to smart_get_action(q[:, p], eps_p, seat=p, obs=<the previous observation>) for both seats,
         step(rows), then smart_state_compact(p) for both players.  features=(shared [N, 2, 34], swarm [N, 2, 12, 13]), both 16-byte aligned: both players'
         compact features; `directions` / `actions_out` int32 [N, 2, 7, 2] receive {swarm, direction} / the rows played, `explored` uint8 [N, 2] 1 where a
-        seat's random branch ran.  No host synchronisation and no allocation per call: it can sit inside a captured loop."""
+        seat's random branch ran.  No host synchronisation and no allocation per call: it can sit inside a captured loop.
+        The head is chosen by q.shape[-1]: 5 as above; 11 is the Minimized agents' (agents/Minimized/training_scripts/dqn_self_play.py; q [N, 2, 12, 11], what
+        a two-set MinimizedQNet writes; evg_step_minimized_q), bit-identical to minimized_get_action(q[:, p], eps_p, seat=p) for both seats, step(rows), then
+        smart_state_compact(p) for both players.  That head has no directions (`directions=` raises ValueError): `actions_out` holds the rows {swarm, node}.
+        league= (11-way head only; evg_step_league_minimized_q): an OpponentLeague plays seat 1 - league.seat as in step_vs_q(), and its "q" member, if it
+        has one, is the second network -- the envs assigned to it take the league seat's rows from q[:, 1 - seat] (dqn_staggered_self_play.py).
+        actions_out[:, league seat] then holds the rows played (the bot's where a bot played, zeros for a frozen bot-played env) and explored[:, league seat]
+        is 2 where a bot played."""
         torch = _torch()
         N = self.num_envs
-        self._user(q, (N, 2, _lib.NUM_GROUPS, 5), torch.float32, "q")
+        minimized = isinstance(q, torch.Tensor) and q.dim() == 4 and q.shape[-1] == _lib.MINI_QNET_OUT
+        if minimized and directions is not None:
+            raise ValueError("the Minimized head (q [N, 2, 12, 11]) has no directions: actions_out holds the rows {swarm, node} the replay memory records")
+        if league is not None and not minimized:
+            raise ValueError("step_q(league=...) exists for the Minimized head (q [N, 2, 12, 11]) only")
+        self._user(q, (N, 2, _lib.NUM_GROUPS, _lib.MINI_QNET_OUT if minimized else 5), torch.float32, "q")
         obs = self.obs if out is None else self._user(out, (N, 2, _lib.OBS_LEN), self.obs_dtype, "out")
         shared = swarm = None
         if features is not None:
@@ -351,12 +363,37 @@ class EvergladesVecEnv(object):
         else:
             eps0 = eps1 = epsilon
         p = self._p
+        if minimized:
+            if league is not None:
+                if not isinstance(league, OpponentLeague):
+                    raise ValueError("league must be an OpponentLeague")
+                rc = self.L.evg_step_league_minimized_q(self._h, C.c_void_p(q.data_ptr()), float(eps0), float(eps1), self._ptr(eps_env),
+                                                        self._league(league, league.seat), int(league.q_member), C.c_void_p(obs.data_ptr()),
+                                                        self._ptr(shared), self._ptr(swarm), self._ptr(actions_out), self._ptr(explored), p["reward"],
+                                                        p["done"], p["winner"], p["scores"], p["status"], self._stream())
+            else:
+                rc = self.L.evg_step_minimized_q(self._h, C.c_void_p(q.data_ptr()), float(eps0), float(eps1), self._ptr(eps_env), C.c_void_p(obs.data_ptr()),
+                                                 self._ptr(shared), self._ptr(swarm), self._ptr(actions_out), self._ptr(explored), p["reward"], p["done"],
+                                                 p["winner"], p["scores"], p["status"], self._stream())
+            if rc:
+                self._check(rc)
+            return obs, self.reward, self.done, self._info
         rc = self.L.evg_step_smart_q(self._h, C.c_void_p(q.data_ptr()), float(eps0), float(eps1), self._ptr(eps_env), C.c_void_p(obs.data_ptr()),
                                      self._ptr(shared), self._ptr(swarm), self._ptr(actions_out), self._ptr(directions), self._ptr(explored),
                                      p["reward"], p["done"], p["winner"], p["scores"], p["status"], self._stream())
         if rc:
             self._check(rc)
         return obs, self.reward, self.done, self._info
+
+    @staticmethod
+    def _bot_league(policy):
+        """`policy` as an OpponentLeague of bots (None: a policy name or id).  A league with a "q" member has no one-seat form: its network member's rows
+        come from the second seat's Q values, which only step_q(league=...) takes."""
+        if not isinstance(policy, OpponentLeague):
+            return None
+        if policy.q_member >= 0:
+            raise ValueError("this league has a \"q\" member (a second network): play it with step_q(q [N, 2, 12, 11], ..., league=league)")
+        return policy
 
     def _league(self, league, seat):
         """the descriptor of `league` for a step of this env (the caller's seat is the league's; an explicit other `seat` is a mistake)"""

@@ -43,7 +43,9 @@ extern "C" {
  *    the opponent league: evg_league_clear / evg_league_assign / evg_league_importance / evg_step_vs_league / evg_step_vs_league_q with their descriptor
  *    evg_league -- added, no layout changed;
  *    the Minimized agents (agents/Minimized: a 59-h1-11 network, one Q per node): evg_minimized_get_action, evg_step_vs_policy_minimized_q,
- *    evg_step_vs_league_minimized_q, evg_minimized_qnet with its descriptor evg_mini_qnet -- added, no layout changed */
+ *    evg_step_vs_league_minimized_q, evg_minimized_qnet with its descriptor evg_mini_qnet -- added, no layout changed;
+ *    Minimized self-play (a network on each seat): evg_step_minimized_q, evg_step_league_minimized_q (a league whose member q_member is the caller's
+ *    second network) -- added, no layout changed */
 /* 6: evg_smart_get_action (DQNAgent.get_action with epsilon > 0), evg_step_vs_policy_smart (the learner-seat turn that also writes the Smart_State
  *    features), evg_get_run_state / evg_set_run_state (agent objects, returns, win counters: checkpoint / resume); reward / score buffers need 8-byte
  *    alignment only (5 asked 16 of every buffer)
@@ -747,6 +749,29 @@ EVG_API int evg_step_vs_policy_minimized_q(evg_handle* h, int seat, const float*
 EVG_API int evg_step_vs_league_minimized_q(evg_handle* h, const float* q, float epsilon, const float* epsilon_env, const evg_league* lg,
                                            void* obs_seat_out, float* shared_out, float* swarm_out, int32_t* actions_out, uint8_t* explored_out,
                                            float* reward_out, uint8_t* done_out, int8_t* winner_out, int32_t* scores_out, uint8_t* status_out, void* stream);
+/* Minimized SELF-PLAY in one launch (agents/Minimized/training_scripts/dqn_self_play.py: a DQNAgent on each seat, both learn): evg_step_smart_q with the
+ * 11-way head -- its argument list without directions_out.  q float32 [N][2][12][11], row [e][p] seat p's network output (what a two-set evg_minimized_qnet
+ * writes in one launch); epsilon0 / epsilon1 the seats' epsilons, or epsilon_env [N][2]; obs_out [N][2][105]; shared_out [N][2][34] / swarm_out
+ * [N][2][12][13] both NULL or both set; actions_out int32 [N][2][7][2] {swarm, node} or NULL; explored_out uint8 [N][2] or NULL.  Alignment rules,
+ * argument checks, error codes (bad input: EVG_ERR_ARG, nothing launched) and launch as evg_step_smart_q; keyed-Philox handles only.  Results -- every
+ * output, and afterwards the handle's state and run state -- are bit for bit those of evg_minimized_get_action(q[:, p], eps_p, seat = p) for p = 0, 1,
+ * evg_step with both seats' rows, evg_smart_state_compact for both players.  Rows are written for every env, frozen ones included. */
+EVG_API int evg_step_minimized_q(evg_handle* h, const float* q, float epsilon0, float epsilon1, const float* epsilon_env, void* obs_out, float* shared_out,
+                                 float* swarm_out, int32_t* actions_out, uint8_t* explored_out, float* reward_out, uint8_t* done_out, int8_t* winner_out,
+                                 int32_t* scores_out, uint8_t* status_out, void* stream);
+/* ... against a league ONE member of which is a network (dqn_staggered_self_play.py: seat 1 drawn once per episode from the second DQN or a scripted bot).
+ * The league lg (layout unchanged) plays seat 1 - lg->seat exactly as in evg_step_vs_league_minimized_q: assignment, per-member tally, redraw at the
+ * episode boundary, object swap, status bits.  q_member in 0..M-1 names the member that is the caller's second network, -1: none (every env bot-played);
+ * anything else is EVG_ERR_ARG.  Where assign[e] == q_member the league seat's rows are evg_minimized_get_action(q[:, 1 - seat], eps, seat = 1 - seat)'s;
+ * members[q_member] must still be a valid EVG_POLICY_* id (evg_league_clear / _assign / _importance are untouched by this), but that bot is never
+ * consulted and the member's object words are carried through swaps unchanged.  The caller's seat is always decoded from q[e][seat].  Outputs as
+ * evg_step_minimized_q (both seats' observations and features: the second network learns too), except:
+ *   actions_out[e][league seat]   the rows PLAYED: the network's where it played, the bot's where a bot played, seven {0, 0} rows for a frozen
+ *                                 bot-played env (its bot is not consulted)
+ *   explored_out[e][league seat]  0 / 1 where the network played, 2 where a bot played (the second learner's own transitions are those != 2) */
+EVG_API int evg_step_league_minimized_q(evg_handle* h, const float* q, float epsilon0, float epsilon1, const float* epsilon_env, const evg_league* lg,
+                                        int q_member, void* obs_out, float* shared_out, float* swarm_out, int32_t* actions_out, uint8_t* explored_out,
+                                        float* reward_out, uint8_t* done_out, int8_t* winner_out, int32_t* scores_out, uint8_t* status_out, void* stream);
 /* The Minimized Q network, inference only (agents/Minimized/QNetwork.py: relu(fc2(relu(fc1(x)))), 59 -> h1 -> 11): evg_smart_qnet's contract -- weights
  * read in place on every call, the fmaf chain acc = b[j], fmaf(W[j][k], x[k], acc) for k ascending, fmaxf(acc, 0) on the hidden layer and (final_relu: the
  * reference applies it) on the output, the compact prefix and one-hot term -- with two layers:

@@ -56,6 +56,8 @@ STEP_FORMS = {"single_turn": (64, 0, 0, 0, 0, 1, 0, 0), "persistent": (64, 1, 0,
               "helper_lanes": (32, 0, 0, 0, 0, 1, 0, 0), "helper_lanes_persistent": (32, 1, 0, 0, 0, 1, 0, 0), "wg256": (64, 0, 0, 0, 0, 4, 0, 0)}
 # evg_step_minimized_kernel<OT, LEAGUE> (SeatQMin, SeatQMinLeague): the one-seat Q form's body with the 11-way head
 MINIMIZED_FORMS = {"seat_q_min": 0, "seat_q_min_league": 1}
+# evg_step_minimized2_kernel<OT, LEAGUE> (TwoSeatQMin, TwoSeatQMinLeague): the two-seat Q form's body with the 11-way head
+MINIMIZED2_FORMS = {"two_seat_q_min": 0, "two_seat_q_min_league": 1}
 OBS_MANGLED = {"float32": "f", "float64": "d", "int16": "s"}
 
 
@@ -64,6 +66,8 @@ def step_kernel_symbol(form, obs_dtype="float32"):
     resource-usage remarks call it"""
     if form in MINIMIZED_FORMS:       # the one-seat Q form with the Minimized agents' 11-way head: a kernel of its own name, <OT, LEAGUE>
         return "_ZN3evg25evg_step_minimized_kernelI%sLb%dEEEvNS_8StepArgsE" % (OBS_MANGLED[obs_dtype], MINIMIZED_FORMS[form])
+    if form in MINIMIZED2_FORMS:      # ... and its two-seat form (Minimized self-play), again a kernel of its own name
+        return "_ZN3evg26evg_step_minimized2_kernelI%sLb%dEEEvNS_8StepArgsE" % (OBS_MANGLED[obs_dtype], MINIMIZED2_FORMS[form])
     lpw, multi, mt, chunked, seat, wpb, qdec, league = STEP_FORMS[form]
     return "_ZN3evg15evg_step_kernelI%sLi%dELb%dELb%dELb%dELb%dELi%dELb%dELb%dEEEvNS_8StepArgsE" % (OBS_MANGLED[obs_dtype], lpw, multi, mt, chunked, seat, wpb,
                                                                                                          qdec, league)
