@@ -3,7 +3,10 @@ agents/Smart_State/Multi_Step.py (NStepModule), utils/reward_shaping.py and DQNA
 device's ring layout so that the tests can compare the metadata record for record.  Vectorised over envs; one call of record() per turn."""
 import numpy as np
 
-SHAPES = ["normalized_score", "basic_reward", "penalize_long_games", "reward_short_games", "transition", "custom"]
+import rng_spec
+
+DRAW_DOMAIN = 5             # counter word 3 of the sample draws
+SHAPES =["normalized_score", "basic_reward", "penalize_long_games", "reward_short_games", "transition", "custom"]
 F_NOT_DONE, F_FINAL = 1, 2
 
 
@@ -112,6 +115,17 @@ class ReplayModel(object):
 
     def size(self):
         return int(self.count.sum(dtype=np.int64))
+
+    def draw(self, seed, call, batch):
+        """The handles int32 [batch, 4] {slot, env, seat, row} of sample(batch, seed) as call number `call`: draw i takes word 0 of
+        Philox((i, call & 0xffffffff, call >> 32, DRAW_DOMAIN), seed), t = (word * total) >> 32, and names the t-th transition in record order."""
+        tr = self.transitions()
+        total = len(tr["slot"])
+        assert total > 0
+        key = rng_spec._key(seed)
+        call = int(call) & 0xFFFFFFFFFFFFFFFF
+        t = [(rng_spec.philox4x32_10((i, call & rng_spec.MASK, call >> 32, DRAW_DOMAIN), key)[0] * total) >> 32 for i in range(int(batch))]
+        return np.stack([tr["slot"][t], tr["env"][t], tr["seat"][t], tr["row"][t]], 1).astype(np.int32)
 
     def transitions(self):
         """Every transition of the memory in the device's record order: dict of arrays slot, env, seat, row, swarm, action, next_slot (-1 where

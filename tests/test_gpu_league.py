@@ -64,13 +64,13 @@ class _Composition(object):
     (scripted_actions), the advanced objects moved out (get_run_state); then step() on the caller's rows and each env's member's rows; the host model tallies,
     draws and swaps at the episode boundaries."""
 
-    def __init__(self, evg, n, seat, dtype, members, weights, resample, auto_reset=True, assign=None):
+    def __init__(self, evg, n, seat, dtype, members, weights, resample, auto_reset=True, assign=None, seed=SEED, env_id_base=0):
         import torch
         self.torch, self.n, self.seat = torch, n, seat
-        self.env = evg.EvergladesVecEnv(n, seed=SEED, obs_dtype=dtype, auto_reset=auto_reset)
+        self.env = evg.EvergladesVecEnv(n, seed=seed, env_id_base=env_id_base, obs_dtype=dtype, auto_reset=auto_reset)
         self.ids = [self.env.POLICIES[m] for m in members]
         self.env.reset()
-        self.model = lm.League(SEED, 0, n, len(members), seat, resample, weights)
+        self.model = lm.League(seed, env_id_base, n, len(members), seat, resample, weights)
         if assign is not None:
             self.model.assign[:] = assign
         self.model.clear(np.zeros(n, np.int64))

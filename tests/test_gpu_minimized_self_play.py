@@ -152,14 +152,14 @@ class _LeagueComposition(object):
     (scripted_actions), the advanced objects moved out (get_run_state); step() plays; the host model tallies, draws and swaps at the episode boundaries.
     The network member's objects do not advance."""
 
-    def __init__(self, evg, n, seat, dtype, members, weights, auto_reset=True):
+    def __init__(self, evg, n, seat, dtype, members, weights, auto_reset=True, seed=cases.SEED, env_id_base=0):
         import torch
         self.torch, self.n, self.seat = torch, n, seat
-        self.env = evg.EvergladesVecEnv(n, seed=cases.SEED, obs_dtype=dtype, auto_reset=auto_reset)
+        self.env = evg.EvergladesVecEnv(n, seed=seed, env_id_base=env_id_base, obs_dtype=dtype, auto_reset=auto_reset)
         self.qm = members.index("q") if "q" in members else -1
         self.ids = [self.env.POLICIES["no_action" if m == "q" else m] for m in members]
         self.env.reset()
-        self.model = lm.League(cases.SEED, 0, n, len(members), seat, True, weights)
+        self.model = lm.League(seed, env_id_base, n, len(members), seat, True, weights)
         self.model.clear(np.zeros(n, np.int64))
         self.live = np.tile(np.asarray(lm.FRESH, np.uint32), (n, 1))
         self.episode = np.zeros(n, np.int64)

@@ -57,6 +57,34 @@ def test_fixture_covers_both_sides_of_the_transition_and_a_short_episode():
     assert (d["a_dirs"][:, :, 1] == 0).any()                                     # rows with direction 0 push nothing
 
 
+def test_draw_names_transitions_in_record_order_and_uses_both_words_of_the_seed():
+    """ReplayModel.draw, the statement of sample()'s draws: every handle names a transition of the memory, draw i is the (word * total) >> 32-th one in
+    record order, a draw below 2^32 / total names the first and the largest word the last; the seed's high word and the call's high word change the draws."""
+    import rng_spec
+    seed = 0x9E3779B97F4A7C15
+    rs = np.random.RandomState(3)
+    m = ReplayModel(5, 2, 6, 1, 0.9)
+    for t in range(9):                                                           # a wrapped ring; every seventh record or so pushes nothing
+        dirs = np.stack([rs.randint(0, 12, (5, 2, 7)), rs.randint(0, 5, (5, 2, 7))], -1).astype(np.int32)
+        m.record(dirs, rs.rand(5, 2).astype(np.float32), rs.rand(5) < 0.15)
+    tr = m.transitions()
+    total = m.size()
+    assert total == len(tr["slot"]) > 100
+    record = (tr["slot"].astype(np.int64) * 5 + tr["env"]) * 2 + tr["seat"]
+    assert (np.diff(record * 8 + tr["row"]) > 0).all()                           # record order, rows ascending within a record
+    valid = set(zip(tr["slot"].tolist(), tr["env"].tolist(), tr["seat"].tolist(), tr["row"].tolist()))
+    h = m.draw(seed, 3, 500)
+    assert h.shape == (500, 4) and h.dtype == np.int32 and set(map(tuple, h.tolist())) <= valid
+    for i in (0, 1, 499):
+        t = (rng_spec.philox4x32_10((i, 3, 0, 5), (seed & 0xFFFFFFFF, seed >> 32))[0] * total) >> 32
+        assert h[i].tolist() == [tr[k][t] for k in ("slot", "env", "seat", "row")]
+    assert len(set(map(tuple, h.tolist()))) > 50                                 # the draws spread over the memory
+    assert not np.array_equal(h, m.draw(seed & 0xFFFFFFFF, 3, 500))              # the seed's high word is part of the key
+    assert not np.array_equal(h, m.draw(seed, 2 ** 32 + 3, 500))                 # the call's high word is part of the counter
+    assert not np.array_equal(h, m.draw(seed, 4, 500))
+    assert np.array_equal(h[:7], m.draw(seed, 3, 7))                             # draw i does not depend on the batch size
+
+
 def _prototype_arity(header, name):
     m = re.search(r"EVG_API int %s\(([^;]*)\)\s*;" % name, header)
     assert m, name
