@@ -1,48 +1,69 @@
 // step_outputs.inc -- fragment of evg_step_kernel's turn loop (step_kernel.inc): the observation image in LDS, the state store, the coalesced
 // observation write-out and the health rows of envs that start a new episode.
-// reads:  gw[12], cntv[12], st[3], L.NW, L.u.A, turn, status, episode, do_reset, valid / nvalid / e0, iter / nturns
+// reads:  gw[12], cntv[12], st[3], L.NW, L.u.A, L.tab.res, turn, status, episode, do_reset, valid / nvalid / e0, iter / nturns
 // writes: L.u.O (the image), io.obs, the state arrays (after the launch's last turn), L.G (next turn's words, persistent form), S.health (restarted envs),
 //         io.feat_shared / io.feat_swarm (one-seat form, two-seat Q form)
     // ---------------- observation of this lane's player (board_state :382-455, player_state :457-501,
     // everglades_env.py:158-171), written as int16 straight into the wave's output image in LDS.
-    // Board part by node ID (every LDS read has a constant offset): slot s of player 1's view shows node p1_node_map[s] (:437-439),
-    // so node n is written to slot p1inv[n]; player 0's view is the identity.
+    // A lane's row of 105 values starts at byte 210 R of the image (R = its row), so nothing wider than a halfword is aligned in a row's own
+    // terms -- stores merged from neighbouring values were 8 / 12 / 16 bytes at 2 or 4 mod 8, which the LDS replays at 64 cycles each (profiles/
+    // r13_a_lds_store_alignment.txt).  The row is therefore assembled in REGISTERS, as the 53 dwords Z[d] = (v[2d], v[2d+1]) of an even row, and stored
+    // on the dword grid of the flat image: an even row's dwords are Z[0..51] themselves, an odd row -- which starts half a dword in -- stores
+    // (v[2d+1], v[2d+2]) = the 64-bit {Z[d+1], Z[d]} shifted right by 16, so ONE v_alignbit_b32 with the per-lane shift 16 (R & 1) serves both
+    // parities.  The halfword left over on the row's odd side (value 104 of an even row, value 0 -- the turn -- of an odd one) is the lane's one 16-bit
+    // store; the two halfwords of a dword that straddles two rows are so written by their own lanes, and no lane touches another's.
+    // Board part by SLOT (the position in the row is then a compile-time one): slot s of player 1's view shows node p1_node_map[s] (:437-439),
+    // player 0's view is the identity -- the node words, the unit counts and the flags are read at that runtime node (aligned 4-byte reads).
     // (a rollout without an observation buffer -- evg_rollout_*(obs_out = NULL): the evaluation harness, which reads only the episode
     // results -- skips the image and the write-out altogether: a sixth of the turn's instructions and 55 % of its bytes)
     const bool want_obs = io.obs != nullptr;
     if (want_obs) {
-    uint32_t nw_n[12], ou_n[12], res_n[12];
+    const uint64_t own_n = player_node_map(P, p1nib);   // nibble s = the node slot s shows = node s in this player's numbering (:485-486)
+    uint32_t nw_s[12], ou_s[12], res_s[12];
 #pragma unroll
-    for (int n = 1; n <= NN; ++n) {
-        nw_n[n] = L.NW[n][E];
-        ou_n[n] = L.u.A[n][col ^ 1];                    // high half: opposing units listed at the node
-        res_n[n] = (uint32_t)L.tab.res[n];              // DEFENSE flag | OBSERVE flag << 16
+    for (int s = 1; s <= NN; ++s) {
+        const uint32_t n = map_node(own_n, (uint32_t)s);
+        nw_s[s] = L.NW[n][E];
+        ou_s[s] = L.u.A[n][col ^ 1];                    // high half: opposing units listed at the node
+        res_s[s] = (uint32_t)L.tab.res[n];              // DEFENSE flag | OBSERVE flag << 16
     }
-    const uint64_t slot_n = P ? L.tab.nib[10] : 0xBA9876543210ull;     // nibble n = board slot of node n in this player's view
-    const uint64_t own_n = player_node_map(P, p1nib);                  // nibble n = node n in this player's numbering (:485-486)
-    WAVE_SYNC();        // A is dead from here on: the union becomes the output image
+    WAVE_SYNC();        // A is dead from here on (the reads above are issued, and the LDS keeps a wave's order): the union becomes the output image
     // one-seat form: the image is [env][105], built by the caller's lane only.  (Splitting that row between the two lanes of the pair -- half the
     // instructions -- and the 28 MB less to write change nothing measurable: 26.7 us either way, like evg_step with both rows; a single-turn launch
     // lasts as long as its slowest SIMD pair, not as long as its instruction or byte count: DESIGN.md section 6.)
-    int16_t* orow = &L.u.O[(SEAT ? E : col) * OBS];
     if (envlane && (!SEAT || P == io.seat)) {
-        orow[0] = (int16_t)turn;
+        int v[OBS];
+        v[0] = turn;
 #pragma unroll
-        for (int n = 1; n <= NN; ++n) {
-            int16_t* o = orow + 4 * (int)((slot_n >> (4 * n)) & 15u) - 3;
-            int v[4];
-            obs_node(v, (int)res_n[n], nw_n[n], (int)(ou_n[n] >> 16));
+        for (int s = 1; s <= NN; ++s) {
+            int t[4];
+            obs_node(t, (int)res_s[s], nw_s[s], (int)(ou_s[s] >> 16));
 #pragma unroll
-            for (int j = 0; j < 4; ++j) o[j] = (int16_t)v[j];
+            for (int j = 0; j < 4; ++j) v[4 * s - 3 + j] = t[j];
         }
 #pragma unroll
         for (int k = 0; k < 12; ++k) {
-            int16_t* o = orow + 45 + 5 * k;
-            int v[5];
-            obs_group(v, gw[k], own_n, (uint32_t)((typ_n >> (4 * k)) & 15u), cntv[k]);
+            int t[5];
+            obs_group(t, gw[k], own_n, (uint32_t)((typ_n >> (4 * k)) & 15u), cntv[k]);
 #pragma unroll
-            for (int j = 0; j < 5; ++j) o[j] = (int16_t)v[j];
+            for (int j = 0; j < 5; ++j) v[45 + 5 * k + j] = t[j];
         }
+        static_assert(OBS == 105, "53 dwords per row, the last one half used");
+        uint32_t Z[OBS / 2 + 1];
+#pragma unroll
+        for (int d = 0; d < OBS / 2; ++d) Z[d] = ((uint32_t)v[2 * d] & 0xFFFFu) | ((uint32_t)v[2 * d + 1] << 16);
+        Z[OBS / 2] = (uint32_t)v[OBS - 1];
+        const uint32_t R = (uint32_t)(SEAT ? E : col), odd = R & 1u;
+        const uint32_t sh = odd << 4;
+        // the row's first whole dword, as an LDS address the compiler takes as given: the 52 stores are then constant dword offsets from ONE register
+        // (left to itself it folds the image's offset in the workgroup's LDS into every store, beyond what a paired store's 8-bit offsets hold,
+        // and forms 26 addresses)
+        typedef __attribute__((address_space(3))) uint32_t lds_u32;
+        lds_u32* ow = (lds_u32*)reinterpret_cast<uint32_t*>(&L.u.O[0]) + ((OBS * R + odd) >> 1);
+        asm("" : "+v"(ow));
+#pragma unroll
+        for (int d = 0; d < OBS / 2; ++d) ow[d] = __builtin_amdgcn_alignbit(Z[d + 1], Z[d], sh);
+        L.u.O[OBS * R + (odd ? 0u : (uint32_t)(OBS - 1))] = (int16_t)(odd ? Z[0] : Z[OBS / 2]);
     }
     }   // want_obs
     PHASE(10);

@@ -2,6 +2,10 @@
 // occupancy.  Each kernel runs UNROLL independent copies of one instruction per loop iteration (8 independent register chains,
 // so dependencies do not limit issue) on a grid of 1 or 2 waves per SIMD; reported: shader cycles per instruction per SIMD
 // (s_memtime of wave 0 / instructions issued by the waves of its SIMD).
+// The LDS store rows (kernel ks) price how the step kernel's observation image is addressed: int16 rows of 105 values, so a lane's row
+// starts at byte lane * 210 and the compiler's merged 8 / 12 / 16-byte stores are misaligned for their size, for every other lane not even
+// dword-aligned.  Each row stores 8 x per unrolled step at constant offsets 16 B apart (the alignment class of the lane address is kept);
+// 14 KB of LDS per wave, so these rows run at 1 and 2 waves per SIMD only.
 //   hipcc -O3 --offload-arch=gfx950 inst_rate.hip -o inst_rate && ./inst_rate
 #include <hip/hip_runtime.h>
 #include <stdio.h>
@@ -75,6 +79,38 @@ __global__ void __launch_bounds__(64) k(uint32_t* out, int iters, uint32_t seed)
     if (threadIdx.x == 0 && blockIdx.x == 0) out[1 << 20] = (uint32_t)(t1 - t0);
 }
 
+typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
+
+template <int MODE>
+__global__ void __launch_bounds__(64) ks(uint32_t* out, int iters, uint32_t seed) {
+    __shared__ uint32_t lds[3584];                      // 14 336 B: the step kernel's union
+    const uint32_t lane = threadIdx.x;
+    uint32_t r[8];
+    uint64_t q[8];
+    u32x4 w[8];
+    for (int i = 0; i < 8; ++i) { r[i] = seed * (i + 3) + lane; q[i] = ((uint64_t)r[i] << 20) | i; w[i] = u32x4{r[i], r[i] + 1, r[i] + 2, r[i] + 3}; }
+    for (int i = lane; i < 3584; i += 64) lds[i] = seed;
+    // highest byte written: 63 * 212 + 7 * 16 + 8 = 13 476 (ds_write2_b32), 63 * 210 + 4 + 7 * 16 + 16 = 13 362 (b128) < 14 336
+    const uint32_t a = MODE <= 1 ? lane * 16 : MODE == 2 || MODE == 4 ? lane * 210 + 2 : MODE == 3 || MODE == 5 ? lane * 210 + 4 : MODE == 6 ? lane * 212 : lane * 210;
+    __syncthreads();
+    const long long t0 = clock64();
+    for (int it = 0; it < iters; ++it) {
+#pragma unroll
+        for (int u = 0; u < 4; ++u) {
+#define S64(i) asm volatile("ds_write_b64 %0, %1 offset:16*" #i :: "v"(a), "v"(q[i]) : "memory");
+#define S128(i) asm volatile("ds_write_b128 %0, %1 offset:16*" #i :: "v"(a), "v"(w[i]) : "memory");
+#define S2X32(i) asm volatile("ds_write2_b32 %0, %1, %2 offset0:4*" #i " offset1:4*" #i "+1" :: "v"(a), "v"(r[i]), "v"(r[(i + 1) & 7]) : "memory");
+#define S16(i) asm volatile("ds_write_b16 %0, %1 offset:16*" #i :: "v"(a), "v"(r[i]) : "memory");
+            if (MODE == 0 || MODE == 2 || MODE == 3) { REP8(S64) } else if (MODE == 1 || MODE == 4 || MODE == 5) { REP8(S128) } else if (MODE == 6) { REP8(S2X32) } else { REP8(S16) }
+        }
+    }
+    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+    const long long t1 = clock64();
+    __syncthreads();
+    out[blockIdx.x * 64 + lane] = lds[(lane * 7) & 63] + lds[lane * 53];
+    if (lane == 0 && blockIdx.x == 0) out[1 << 20] = (uint32_t)(t1 - t0);
+}
+
 typedef void (*kern_t)(uint32_t*, int, uint32_t);
 template <int M> struct Tab { static void fill(kern_t* t) { t[M] = k<M>; Tab<M - 1>::fill(t); } };
 template <> struct Tab<-1> { static void fill(kern_t*) {} };
@@ -103,6 +139,28 @@ int main() {
             uint32_t cyc; hipMemcpy(&cyc, dmem + (1 << 20), 4, hipMemcpyDeviceToHost);
             const double n = (double)iters * 32.0;
             printf("%-28s wave 0: %6.2f cycles per own instruction = %6.2f cycles per instruction issued on its SIMD   (%.3f ms = %.2f cycles of 2.4 GHz per instruction per SIMD)\n", names[m], cyc / n, cyc / n / wps, ms, ms * 1e-3 * 2.4e9 / (n * wps));
+            hipEventDestroy(e0); hipEventDestroy(e1);
+        }
+    }
+    // ---- LDS store addressing (the observation image): 1 and 2 waves per SIMD
+    const char* snames[8] = {"ds_write_b64  lane*16", "ds_write_b128 lane*16", "ds_write_b64  lane*210+2", "ds_write_b64  lane*210+4", "ds_write_b128 lane*210+2",
+                             "ds_write_b128 lane*210+4", "ds_write2_b32 lane*212", "ds_write_b16  lane*210"};
+    kern_t stab[8] = {ks<0>, ks<1>, ks<2>, ks<3>, ks<4>, ks<5>, ks<6>, ks<7>};
+    for (int wps = 1; wps <= 2; wps *= 2) {
+        const int grid = 1024 * wps;
+        printf("---- LDS stores, %d wave(s) per SIMD (%d workgroups of 64, 14 KB of LDS each)\n", wps, grid);
+        for (int m = 0; m < 8; ++m) {
+            hipEvent_t e0, e1; hipEventCreate(&e0); hipEventCreate(&e1);
+            float ms = 0;
+            for (int rep = 0; rep < 2; ++rep) {
+                hipEventRecord(e0);
+                hipLaunchKernelGGL(stab[m], dim3(grid), dim3(64), 0, 0, dmem, iters / 4, 12345u);
+                hipEventRecord(e1); hipEventSynchronize(e1);
+                hipEventElapsedTime(&ms, e0, e1);
+            }
+            uint32_t cyc; hipMemcpy(&cyc, dmem + (1 << 20), 4, hipMemcpyDeviceToHost);
+            const double n = (double)(iters / 4) * 32.0;
+            printf("%-28s wave 0: %6.2f cycles per own instruction = %6.2f cycles per instruction issued on its SIMD   (%.3f ms = %.2f cycles of 2.4 GHz per instruction per SIMD)\n", snames[m], cyc / n, cyc / n / wps, ms, ms * 1e-3 * 2.4e9 / (n * wps));
             hipEventDestroy(e0); hipEventDestroy(e1);
         }
     }

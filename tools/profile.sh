@@ -18,10 +18,10 @@ for FORM in ${FORMS:-persistent perturn caller learner}; do
   EXTRA=""; if [ $FORM = caller ]; then EXTRA="--caller-actions"; fi; if [ $FORM = learner ]; then EXTRA="--learner-seat"; fi
   CMD="python3 $R/bench.py --full --steps 150 --warmup 150 --repeats 1 --sustained-launches 0 --no-cpu-baseline --no-extra-legs --turns-per-launch $TPL $EXTRA $*"
   echo "$CMD" > $OUT/cmd_$FORM.txt
-  rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/${FORM}_stats -- $CMD > $OUT/bench_${FORM}_stats.json 2> $OUT/${FORM}_stats.err || exit 1
-  rocprofv3 --kernel-trace --pmc FETCH_SIZE --output-format csv -d $OUT/${FORM}_fetch -- $CMD > $OUT/bench_${FORM}_fetch.json 2> $OUT/${FORM}_fetch.err || exit 1
-  rocprofv3 --kernel-trace --pmc WRITE_SIZE --output-format csv -d $OUT/${FORM}_write -- $CMD > $OUT/bench_${FORM}_write.json 2> $OUT/${FORM}_write.err || exit 1
+  timeout -k 10 ${STEP_TIMEOUT:-300} rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/${FORM}_stats -- $CMD > $OUT/bench_${FORM}_stats.json 2> $OUT/${FORM}_stats.err || exit 1
+  timeout -k 10 ${STEP_TIMEOUT:-300} rocprofv3 --kernel-trace --pmc FETCH_SIZE --output-format csv -d $OUT/${FORM}_fetch -- $CMD > $OUT/bench_${FORM}_fetch.json 2> $OUT/${FORM}_fetch.err || exit 1
+  timeout -k 10 ${STEP_TIMEOUT:-300} rocprofv3 --kernel-trace --pmc WRITE_SIZE --output-format csv -d $OUT/${FORM}_write -- $CMD > $OUT/bench_${FORM}_write.json 2> $OUT/${FORM}_write.err || exit 1
 done
-rocprofv3 --kernel-trace --pmc FETCH_SIZE --output-format csv -d $OUT/calib_fetch -- python3 $R/tools/pmc_calib.py > $OUT/calib_fetch.log 2>&1 || exit 1
-rocprofv3 --kernel-trace --pmc WRITE_SIZE --output-format csv -d $OUT/calib_write -- python3 $R/tools/pmc_calib.py > $OUT/calib_write.log 2>&1 || exit 1
+timeout -k 10 ${STEP_TIMEOUT:-300} rocprofv3 --kernel-trace --pmc FETCH_SIZE --output-format csv -d $OUT/calib_fetch -- python3 $R/tools/pmc_calib.py > $OUT/calib_fetch.log 2>&1 || exit 1
+timeout -k 10 ${STEP_TIMEOUT:-300} rocprofv3 --kernel-trace --pmc WRITE_SIZE --output-format csv -d $OUT/calib_write -- python3 $R/tools/pmc_calib.py > $OUT/calib_write.log 2>&1 || exit 1
 find $OUT -name "*.csv" | wc -l
