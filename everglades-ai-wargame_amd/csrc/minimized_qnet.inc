@@ -7,7 +7,8 @@
 //
 // Numerics: as qnet_kernels.inc -- a sequence of 16x16x4 MFMAs over k-steps 0, 1, 2, ... with C = the bias IS the chain acc = b[j], fmaf(W[j][k], x[k], acc)
 // for k ascending; operands in natural k order, padded k positions with zero weight and zero input; the compact layouts run the 34-term shared prefix once
-// per 16 envs and add the one-hot term W1[j][47 + s] on the VALU.
+// per 16 envs and add the one-hot term W1[j][47 + s] on the VALU.  The ReLU is torch's (a NaN stays a NaN, hidden layer and output), and the padded
+// hidden units inside the last tile (index >= h1) are exact zeros whatever their accumulator holds (0 + sum of x * 0 is NaN for a non-finite x): zeroed once, never stored to.
 //
 // Hidden up to 128 is up to 8 column tiles of 16; the 11 outputs are one tile.  Tiles beyond the network's h1 are skipped (wave-uniform branches), so a
 // network of 80 runs 5.  Registers hold what every group of rows reuses and fits: the 13 swarm columns of W1 (compact; 4 k-steps x 8 tiles), W2 (32 k-steps)
@@ -16,7 +17,7 @@
 // in, A layout out); Q leaves the accumulator straight to HBM: a row's 11 values are 44 contiguous bytes.
 
 constexpr int MQ_OUT = 11, MQ_H = 128, MQ_TILES = MQ_H / 16;   // output width, the largest hidden size, its column tiles
-constexpr int MQ_HS = 132;                                     // row stride of the hidden tile in LDS (132 = 4 mod 64: the A-layout read is conflict-free)
+constexpr int MQ_HS = 132;                                     // row stride of the hidden tile in LDS (132 = 4 mod 64: the A-layout read is conflict-free; 4 spare columns)
 constexpr int MQ_W1S = 61, MQ_W1PS = 37;                       // row strides of the staged W1 (expanded: 60 columns) and of its shared columns (compact: 36)
 constexpr int MQ_KX = 15, MQ_KP = 9, MQ_KS = 4, MQ_K2 = MQ_H / 4;   // k-steps: expanded layer 1, compact prefix, swarm columns, layer 2
 
@@ -37,7 +38,7 @@ struct MiniQnetArgs {
 };
 
 // layer 2 of 16 rows whose hidden layer (after the ReLU) is in tile ht: the Q tile (D layout; columns 0..10 are Q)
-// (k runs over the nt column tiles layer 1 wrote: k >= h1 inside the last tile has a zero weight and a zero input)
+// (k runs over the nt column tiles layer 1 wrote: k >= h1 inside the last tile has a zero weight and an exact zero input: qn_store_col)
 __device__ __forceinline__ qn_f4 mq_layer2(const float* __restrict__ ht, const float (&w2f)[MQ_K2], float b2v, int nt, int final_relu, int lane) {
     const int arow = (lane & 15) * MQ_HS + (lane >> 4);
     qn_f4 q = qn_f4{b2v, b2v, b2v, b2v};
@@ -48,15 +49,16 @@ __device__ __forceinline__ qn_f4 mq_layer2(const float* __restrict__ ht, const f
             for (int st = 4 * t; st < 4 * t + 4; ++st) q = qn_mfma(ht[arow + 4 * st], w2f[st], q);
     if (final_relu)
 #pragma unroll
-        for (int r = 0; r < 4; ++r) q[r] = fmaxf(q[r], 0.0f);
+        for (int r = 0; r < 4; ++r) q[r] = qn_relu(q[r]);
     return q;
 }
 
-// acc (D layout) of column tile t -> relu -> the hidden tile
-__device__ __forceinline__ void mq_store_hidden(float* __restrict__ ht, const qn_f4 acc, int t, int lane) {
-    const int row0 = 4 * (lane >> 4), col = lane & 15;
+// acc (D layout) of a column tile -> relu (qn_relu: a NaN stays) -> column c of the hidden tile (qn_store_col: the padded units of the last tile,
+// >= h1, go to the row's spare columns 128..131, and theirs keep the exact zeros the tile was filled with before the wavefront's first group)
+__device__ __forceinline__ void mq_store_hidden(float* __restrict__ ht, const qn_f4 acc, int c, int lane) {
+    const int row0 = 4 * (lane >> 4);
 #pragma unroll
-    for (int r = 0; r < 4; ++r) ht[(row0 + r) * MQ_HS + 16 * t + col] = fmaxf(acc[r], 0.0f);
+    for (int r = 0; r < 4; ++r) ht[(row0 + r) * MQ_HS + c] = qn_relu(acc[r]);
 }
 
 template <bool EXPANDED>
@@ -107,9 +109,13 @@ __global__ void __launch_bounds__(64 * QN_WAVES) evg_mini_qnet_kernel(MiniQnetAr
 #pragma unroll
     for (int t = 0; t < MQ_TILES; ++t) b1v[t] = 16 * t + col < H1 ? W.b1[16 * t + col] : 0.0f;
     const float b2v = col < MQ_OUT ? W.b2[col] : 0.0f;
+    float* ht = tiles[wave];
+    int cols[MQ_TILES];                               // where this lane's units of the hidden layer are stored
+#pragma unroll
+    for (int t = 0; t < MQ_TILES; ++t) cols[t] = qn_store_col(t, col, H1, MQ_H);
+    qn_zero_tile(ht, 16 * MQ_HS, lane);               // the padded columns of the last tile are zeros from here on
     __syncthreads();
 
-    float* ht = tiles[wave];
     const int row0 = 4 * kq;
     const long long R = a.rows;
     const long long groups = (R + 15) >> 4;
@@ -136,7 +142,7 @@ __global__ void __launch_bounds__(64 * QN_WAVES) evg_mini_qnet_kernel(MiniQnetAr
                     qn_f4 acc = qn_f4{b1v[t], b1v[t], b1v[t], b1v[t]};
 #pragma unroll
                     for (int st = 0; st < MQ_KX; ++st) acc = qn_mfma(xa[st], wl[(16 * t + col) * MQ_W1S + 4 * st + kq], acc);
-                    mq_store_hidden(ht, acc, t, lane);
+                    mq_store_hidden(ht, acc, cols[t], lane);
                 }
             qn_wave_sync();
             const qn_f4 q = mq_layer2(ht, w2f, b2v, nt, a.final_relu, lane);
@@ -181,7 +187,7 @@ __global__ void __launch_bounds__(64 * QN_WAVES) evg_mini_qnet_kernel(MiniQnetAr
                         const float oh = wl[MQ_H * MQ_W1PS + s * MQ_H + 16 * t + col];   // the one-hot term at position 47 + s
 #pragma unroll
                         for (int r = 0; r < 4; ++r) acc[r] = acc[r] + oh;
-                        mq_store_hidden(ht, acc, t, lane);
+                        mq_store_hidden(ht, acc, cols[t], lane);
                     }
                 if (s + 1 < 12) {                     // the next swarm's inputs, in flight during this swarm's layer 2
                     asm volatile("" : "+v"(kv));

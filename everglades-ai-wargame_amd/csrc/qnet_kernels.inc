@@ -7,7 +7,9 @@
 // Numerics.  v_mfma_f32_16x16x4_f32 computes D[i][j] = fma(A[i][3] B[3][j], fma(A[i][2] B[2][j], fma(A[i][1] B[1][j], fma(A[i][0] B[0][j], C[i][j]))))
 // exactly (one rounding per product, k ascending), so a sequence of them over k-steps 0, 1, 2, ... with C = the bias IS the chain of the contract.
 // The operands are always taken in natural k order (the hidden tiles go through LDS, never accumulator-as-operand), and every padded k position has a
-// zero weight and a zero input, which leaves the chain unchanged.  The compact layouts run the chain prefix b1 + shared[0..33] once per 16 envs and
+// zero weight and a zero input, which leaves the chain unchanged.  The zero input is enforced, not incidental: the ReLU is torch's (x < 0 ? 0 : x, a NaN
+// stays a NaN, on the hidden layers and on the output), so a padded hidden unit -- whose accumulator is 0 + sum of x * 0, NaN for an Inf or NaN x -- is
+// an exact zero in the tile (zeroed once, never stored to: qn_store_col); otherwise NaN * 0 would poison every output of a row that has one non-finite input.  The compact layouts run the chain prefix b1 + shared[0..33] once per 16 envs and
 // continue it per swarm with swarm[s][0..12] (W1 columns 34..46), then add W1[j][47 + s] on the VALU: the one-hot term.
 //
 // Lane maps (16x16x4 f32): A lane l = X[row l & 15][k l >> 4], B lane l = W[column l & 15][k l >> 4], C/D lane l register r = [row 4 (l >> 4) + r]
@@ -16,7 +18,7 @@
 
 constexpr int QN_IN = 59, QN_OUT = 5, QN_H = 64;       // input width, output width, the largest hidden size
 constexpr int QN_WAVES = 4;                            // wavefronts per workgroup
-constexpr int QN_HS = 68;                              // row stride of a hidden tile in LDS (68 = 4 mod 64: the A-layout read is conflict-free)
+constexpr int QN_HS = 68;                              // row stride of a hidden tile in LDS (68 = 4 mod 64: the A-layout read is conflict-free; the 4 spare columns take the padded units)
 constexpr int QN_W1S = 61, QN_W2S = 65, QN_W3S = 65;   // row strides of the staged weights (odd: the B-fragment reads spread over the banks)
 constexpr int QN_STAGE = QN_H * QN_W1S + QN_H * QN_W2S + 16 * QN_W3S;   // staged weights (floats)
 constexpr int QN_WAVE_LDS = 2 * 16 * QN_HS + 16 * 60;                    // per wavefront: two hidden tiles and the 16 x 60 Q tile
@@ -52,18 +54,33 @@ __device__ __forceinline__ void qn_wave_sync() {
     __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
 }
 
-// acc (D layout) -> relu -> hidden tile in LDS
-__device__ __forceinline__ void qn_store_hidden(float* __restrict__ tile, const qn_f4 (&acc)[4], int lane) {
-    const int row0 = 4 * (lane >> 4), col = lane & 15;
+// torch.relu: a NaN stays a NaN (fmaxf would drop it); the sign of a zero result is not part of the contract.  IEEE 754-2019 maximum, which gfx950 has
+// as one instruction (v_maximum3_f32), so the ReLU costs what fmaxf cost
+__device__ __forceinline__ float qn_relu(float x) { return __builtin_elementwise_maximum(x, 0.0f); }
+
+// The column of a hidden tile that unit 16 t + col of a layer of hn units is stored to: its own -- or, for a padded unit (>= hn), one of the row's four
+// spare columns (the row stride is 64 + 4), which nothing reads.  A padded unit's accumulator is 0 + sum of x * 0, a NaN as soon as an x is Inf or NaN,
+// which the next layer's zero weight would not take out (NaN * 0); stored aside, it leaves the padded columns with the exact zeros that qn_zero_tile
+// wrote once, before the wavefront's first group.  Lane-constant, computed before the loop over the groups: the stores stay unconditional.
+__device__ __forceinline__ int qn_store_col(int t, int col, int hn, int width) { return 16 * t + col < hn ? 16 * t + col : width + (col & 3); }
+
+// acc (D layout) -> relu -> hidden tile in LDS, tile t to column cols[t] (qn_store_col)
+__device__ __forceinline__ void qn_store_hidden(float* __restrict__ tile, const qn_f4 (&acc)[4], const int (&cols)[4], int lane) {
+    const int row0 = 4 * (lane >> 4);
 #pragma unroll
     for (int t = 0; t < 4; ++t)
 #pragma unroll
-        for (int r = 0; r < 4; ++r) tile[(row0 + r) * QN_HS + 16 * t + col] = fmaxf(acc[t][r], 0.0f);
+        for (int r = 0; r < 4; ++r) tile[(row0 + r) * QN_HS + cols[t]] = qn_relu(acc[t][r]);
+}
+
+// a wavefront's n floats of LDS <- exact zeros (the padded columns of its hidden tiles are never written again)
+__device__ __forceinline__ void qn_zero_tile(float* __restrict__ tile, int n, int lane) {
+    for (int i = lane; i < n; i += 64) tile[i] = 0.0f;
 }
 
 // Layers 2 and 3 of 16 rows whose first hidden layer (after the ReLU) is in tile h1t: returns the Q tile (D layout; columns 0..4 are Q)
 __device__ __forceinline__ qn_f4 qn_layers23(const float* __restrict__ h1t, float* __restrict__ h2t, const float (&w2f)[16][4], const float (&w3f)[16],
-                                            const float (&b2v)[4], float b3v, int n2, int final_relu, int lane) {
+                                            const float (&b2v)[4], float b3v, int n2, const int (&cols2)[4], int final_relu, int lane) {
     const int arow = (lane & 15) * QN_HS + (lane >> 4);
     qn_f4 acc[4];
 #pragma unroll
@@ -76,14 +93,14 @@ __device__ __forceinline__ qn_f4 qn_layers23(const float* __restrict__ h1t, floa
             for (int t = 0; t < 4; ++t) acc[t] = qn_mfma(a, w2f[st][t], acc[t]);
         }
     }
-    qn_store_hidden(h2t, acc, lane);
+    qn_store_hidden(h2t, acc, cols2, lane);
     qn_wave_sync();
     qn_f4 q = qn_f4{b3v, b3v, b3v, b3v};
 #pragma unroll
     for (int st = 0; st < 16; ++st) q = qn_mfma(h2t[arow + 4 * st], w3f[st], q);   // (k >= h2: zero weight, zero input)
     if (final_relu)
 #pragma unroll
-        for (int r = 0; r < 4; ++r) q[r] = fmaxf(q[r], 0.0f);
+        for (int r = 0; r < 4; ++r) q[r] = qn_relu(q[r]);
     return q;
 }
 
@@ -162,6 +179,14 @@ __global__ void __launch_bounds__(64 * QN_WAVES) evg_qnet_kernel(QnetArgs a) {
     float* h1t = lds + wave * QN_WAVE_LDS;
     float* h2t = h1t + 16 * QN_HS;
     float* qt = h2t + 16 * QN_HS;
+    int cols1[4], cols2[4];                           // where this lane's units of the two hidden layers are stored
+#pragma unroll
+    for (int t = 0; t < 4; ++t) {
+        cols1[t] = qn_store_col(t, col, H1, QN_H);
+        cols2[t] = qn_store_col(t, col, H2, QN_H);
+    }
+    qn_zero_tile(h1t, 2 * 16 * QN_HS, lane);          // both hidden tiles: what was staged there is gone, the padded columns are zeros from here on
+    qn_wave_sync();
     const int n2 = (H1 + 3) >> 2;                     // layer-2 k-steps (layer 3 always runs 16: its padded k have zero weights and inputs)
     const int row0 = 4 * kq;
     const long long R = a.rows;
@@ -186,9 +211,9 @@ __global__ void __launch_bounds__(64 * QN_WAVES) evg_qnet_kernel(QnetArgs a) {
             for (int st = 0; st < 15; ++st)
 #pragma unroll
                 for (int t = 0; t < 4; ++t) acc[t] = qn_mfma(xa[st], w1f[st][t], acc[t]);
-            qn_store_hidden(h1t, acc, lane);
+            qn_store_hidden(h1t, acc, cols1, lane);
             qn_wave_sync();
-            const qn_f4 q = qn_layers23(h1t, h2t, w2f, w3f, b2v, b3v, n2, a.final_relu, lane);
+            const qn_f4 q = qn_layers23(h1t, h2t, w2f, w3f, b2v, b3v, n2, cols2, a.final_relu, lane);
             if (col < QN_OUT)
 #pragma unroll
                 for (int r = 0; r < 4; ++r) qt[(row0 + r) * QN_OUT + col] = q[r];
@@ -237,9 +262,9 @@ __global__ void __launch_bounds__(64 * QN_WAVES) evg_qnet_kernel(QnetArgs a) {
 #pragma unroll
                     for (int r = 0; r < 4; ++r) acc[t][r] = acc[t][r] + oh;
                 }
-                qn_store_hidden(h1t, acc, lane);
+                qn_store_hidden(h1t, acc, cols1, lane);
                 qn_wave_sync();
-                const qn_f4 q = qn_layers23(h1t, h2t, w2f, w3f, b2v, b3v, n2, a.final_relu, lane);
+                const qn_f4 q = qn_layers23(h1t, h2t, w2f, w3f, b2v, b3v, n2, cols2, a.final_relu, lane);
                 if (col < QN_OUT)
 #pragma unroll
                     for (int r = 0; r < 4; ++r) qt[(row0 + r) * 60 + s * QN_OUT + col] = q[r];

@@ -625,8 +625,11 @@ EVG_API int evg_replay_gather(evg_handle* h, const evg_replay* m, int batch, con
  * every call, so an optimizer step or a load_state_dict takes effect without rebinding.  Training (autograd, the optimizer) stays with the consumer.
  *   set p:   w1[p] [h1][59], b1[p] [h1], w2[p] [h2][h1], b2[p] [h2], w3[p] [5][h2], b3[p] [5]           h1, h2 in 1..64
  * Numerics (bit-exact, reproducible by a host model): every pre-activation is acc = b[j], then acc = fmaf(W[j][k], x[k], acc) for k ascending over the
- * layer's input index; then fmaxf(acc, 0) on the two hidden layers, and on the output layer when final_relu is set (the reference's QNetwork applies
- * it).  Input row of a compact layout: x = shared(34) ++ swarm[s](13) ++ onehot(s)(12); the chain's prefix b1[j] + the 34 shared terms is computed once
+ * layer's input index; then torch's ReLU, acc < 0 ? 0 : acc, on the two hidden layers, and on the output layer when final_relu is set (the reference's
+ * QNetwork applies it).  A NaN stays a NaN through every ReLU (not fmaxf, which would drop it: a diverged network must not look finite); Inf, overflow
+ * inside the chain, Inf * 0 = NaN and subnormals (kept, never flushed) all follow the IEEE fmaf chain.  The sign of a zero is not part of the contract.
+ * Padding is never visible: hidden units the kernel pads a layer with (index >= h1, >= h2) enter the next layer as exact zeros whatever the row holds,
+ * so a non-finite input reaches exactly the outputs the chain says it reaches and no other row.  Input row of a compact layout: x = shared(34) ++ swarm[s](13) ++ onehot(s)(12); the chain's prefix b1[j] + the 34 shared terms is computed once
  * per env and continued per swarm, the one-hot term at position 47 + s is acc + w1[j][47 + s] (a zero term leaves the chain unchanged), so the compact
  * and the expanded layouts give equal Q for the same features.
  * Layouts (rows R; any R >= 1 up to 2^30, independent of the handle's N: the handle only names the device):
@@ -642,7 +645,7 @@ enum { EVG_QNET_COMPACT = 0, EVG_QNET_COMPACT_SEATS = 1, EVG_QNET_EXPANDED = 2 }
 typedef struct evg_qnet {
     uint32_t struct_size;          /* sizeof(evg_qnet)                                                                      */
     int32_t h1, h2;                /* hidden sizes, 1..64 (fc1_size / fc2_size of the reference's pickles; default 60 / 60)  */
-    int32_t final_relu;            /* 0 / 1: fmaxf(q, 0) on the output layer                                                */
+    int32_t final_relu;            /* 0 / 1: the ReLU (q < 0 ? 0 : q, NaN kept) on the output layer                         */
     int32_t num_sets;              /* 1, or 2 for EVG_QNET_COMPACT_SEATS                                                    */
     const float* w1[2];
     const float* b1[2];
@@ -773,8 +776,9 @@ EVG_API int evg_step_league_minimized_q(evg_handle* h, const float* q, float eps
                                         int q_member, void* obs_out, float* shared_out, float* swarm_out, int32_t* actions_out, uint8_t* explored_out,
                                         float* reward_out, uint8_t* done_out, int8_t* winner_out, int32_t* scores_out, uint8_t* status_out, void* stream);
 /* The Minimized Q network, inference only (agents/Minimized/QNetwork.py: relu(fc2(relu(fc1(x)))), 59 -> h1 -> 11): evg_smart_qnet's contract -- weights
- * read in place on every call, the fmaf chain acc = b[j], fmaf(W[j][k], x[k], acc) for k ascending, fmaxf(acc, 0) on the hidden layer and (final_relu: the
- * reference applies it) on the output, the compact prefix and one-hot term -- with two layers:
+ * read in place on every call, the fmaf chain acc = b[j], fmaf(W[j][k], x[k], acc) for k ascending, torch's ReLU (acc < 0 ? 0 : acc: a NaN stays a NaN) on the hidden
+ * layer and (final_relu: the reference applies it) on the output, padded hidden units (index >= h1) entering layer 2 as exact zeros, the compact prefix
+ * and one-hot term -- with two layers:
  *   set p:   w1[p] [h1][59], b1[p] [h1], w2[p] [11][h1], b2[p] [11]           h1 in 1..128 (fc1_size of the reference's pickles; default 80)
  * Layouts and row limits as evg_smart_qnet, q_out [R][12][11], [R][2][12][11] or [R][11].  Refused with EVG_ERR_INVALID (nothing launched):
  * struct_size != sizeof(evg_mini_qnet), h1 outside 1..128, final_relu not 0/1, an unknown layout, a num_sets the layout does not take, a NULL or not
@@ -783,7 +787,7 @@ EVG_API int evg_step_league_minimized_q(evg_handle* h, const float* q, float eps
 typedef struct evg_mini_qnet {
     uint32_t struct_size;          /* sizeof(evg_mini_qnet)                                        */
     int32_t h1;                    /* hidden size, 1..128                                          */
-    int32_t final_relu;            /* 0 / 1: fmaxf(q, 0) on the output layer                       */
+    int32_t final_relu;            /* 0 / 1: the ReLU (NaN kept) on the output layer               */
     int32_t num_sets;              /* 1, or 2 for EVG_QNET_COMPACT_SEATS                           */
     const float* w1[2];
     const float* b1[2];

@@ -58,7 +58,8 @@ def get_action(q, seed, env_ids, episodes, turns, player, eps):
 
 
 def forward(x, params, final_relu):
-    """Expanded rows x [..., 59] -> Q [..., 11]: relu(fc2(relu(fc1(x)))) by the float32 fmaf chain."""
+    """Expanded rows x [..., 59] -> Q [..., 11]: relu(fc2(relu(fc1(x)))) by the float32 fmaf chain; the ReLU is torch's (qnet_model.layer: a NaN stays
+    a NaN, on the hidden layer and on the output), and the model has no padded units."""
     w1, b1, w2, b2 = params
     lead = x.shape[:-1]
     h = layer(np.asarray(x, np.float32).reshape(-1, 59), w1, b1, True)

@@ -1,12 +1,14 @@
 """Host model of the device Q network (everglades_amd.SmartQNet, include/evg.h evg_smart_qnet): the numerics contract restated in numpy.  Every
-pre-activation is acc = b[j], then acc = fmaf(W[j][k], x[k], acc) for k ascending, then fmaxf(acc, 0) on the hidden layers (and on the output with
-final_relu).  Python has no exact fp32 fma, so fmaf32 emulates it in float64: the product of two fp32 values is exact in float64, the sum is taken
+pre-activation is acc = b[j], then acc = fmaf(W[j][k], x[k], acc) for k ascending, then torch's ReLU (acc < 0 ? 0 : acc; np.maximum: a NaN stays
+a NaN, the sign of a zero is not part of the contract) on the hidden layers (and on the output with final_relu).  The model has no padded units.  Python has no exact fp32 fma, so fmaf32 emulates it in float64: the product of two fp32 values is exact in float64, the sum is taken
 with TwoSum, and the rounding to fp32 is settled by the TwoSum error where the float64 sum lies exactly halfway between two fp32 values."""
 import numpy as np
 
 
 def fmaf32(a, b, c):
-    """Exactly rounded fp32 fma(a, b, c), elementwise (finite inputs whose product and sum do not overflow fp32)."""
+    """Exactly rounded fp32 fma(a, b, c), elementwise, over the whole of fp32: subnormal operands and results, overflow to Inf, NaN, +-Inf, Inf * 0 and
+    Inf - Inf (float64 carries all of them, and its double rounding through float64 is settled by the TwoSum error); tests/test_qnet_host.py compares it
+    with libm's fmaf class by class."""
     a, b, c = (np.asarray(v, np.float32).astype(np.float64) for v in (a, b, c))
     p = a * b                                          # exact: 24 + 24 bits
     s = p + c

@@ -71,6 +71,65 @@ def test_fma_emulation_on_constructed_ties():
     assert np.array_equal(_bits(fmaf32(a, b, c)), _bits(want))
 
 
+def _class_triples(name, n, rng):
+    """n random fp32 triples (a, b, c) of one exponent class of a * b + c"""
+    def val(lo, hi):
+        return (rng.choice([-1.0, 1.0], n) * (1.0 + rng.random(n)) * np.exp2(rng.integers(lo, hi, n))).astype(np.float32)
+    if name == "normal":
+        return val(-30, 30), val(-30, 30), val(-60, 60)
+    if name == "subnormal product, subnormal addend":
+        return val(-80, -60), val(-89, -66), val(-149, -126)
+    if name == "subnormal x normal":
+        return val(-149, -126), val(-8, 8), val(-149, -120)
+    if name == "overflow":
+        return val(60, 127), val(0, 68), val(100, 128)
+    return val(-149, 128), val(-149, 128), val(-149, 128)                    # the full range
+
+
+CLASSES = ["normal", "subnormal product, subnormal addend", "subnormal x normal", "overflow", "full range"]
+
+
+def _same(got, want):
+    """equal NaN masks, equal bits elsewhere (a NaN's sign and payload are not part of the contract)"""
+    got, want = np.asarray(got, np.float32), np.asarray(want, np.float32)
+    nan = np.isnan(want)
+    return np.array_equal(np.isnan(got), nan) and np.array_equal(_bits(got)[~nan], _bits(want)[~nan])
+
+
+@pytest.mark.parametrize("name", CLASSES)
+def test_fma_emulation_equals_libm_fmaf_in_every_exponent_class(name):
+    """The emulation holds over the whole of fp32 -- subnormal operands and results, overflow to Inf -- not only where product and sum stay normal."""
+    rng = np.random.default_rng(CLASSES.index(name) + 11)
+    a, b, c = _class_triples(name, 4000, rng)
+    f = _libm_fmaf()
+    want = np.array([f(float(x), float(y), float(z)) for x, y, z in zip(a, b, c)], np.float32)
+    with np.errstate(all="ignore"):
+        got = fmaf32(a, b, c)
+    assert _same(got, want)
+    tiny = np.finfo(np.float32).tiny
+    if "subnormal" in name:                                                  # the class reaches what it names
+        assert ((np.abs(want) < tiny) & (want != 0)).mean() > 0.2
+    if name == "overflow":
+        assert 0.2 < np.isinf(want).mean() < 0.999
+    if name == "full range":
+        assert np.isinf(want).any() and (np.abs(want) < tiny).any() and np.isfinite(want).mean() > 0.3
+
+
+def test_fma_emulation_on_non_finite_operands_and_signed_zeros():
+    inf, nan, big = np.inf, np.nan, 3.0e38
+    cases = [(nan, 1, 1), (1, nan, 1), (1, 1, nan), (inf, 2, 1), (-inf, 2, 1), (2, inf, -1), (1, 1, inf), (1, 1, -inf), (inf, 0, 1), (0, -inf, 1),
+             (inf, 0, nan), (inf, 1, -inf), (-inf, 1, inf), (inf, -1, inf), (inf, 1, inf), (-inf, -1, -inf), (big, 2, -inf), (big, big, -big),
+             (big, -big, big), (big, 2, -big), (0.0, 1, 0.0), (-0.0, 1, 0.0), (-0.0, 1, -0.0), (0.0, -1, -0.0), (1, 1, -1), (-1, 1, 1), (0.0, 5, -0.0),
+             (1e-30, 1e-30, 0.0), (1e-30, -1e-30, 0.0), (1e-30, -1e-30, -0.0), (1e-45, 0.5, 0.0), (1e-45, 0.5, 1e-45)]
+    a, b, c = (np.array(v, np.float32) for v in zip(*cases))
+    f = _libm_fmaf()
+    want = np.array([f(float(x), float(y), float(z)) for x, y, z in zip(a, b, c)], np.float32)
+    with np.errstate(all="ignore"):
+        got = fmaf32(a, b, c)
+    assert _same(got, want)
+    assert np.isnan(want).sum() >= 8 and np.isinf(want).sum() >= 8
+
+
 def _params(d, v):
     return tuple(d[v + "_" + k] for k in ("w1", "b1", "w2", "b2", "w3", "b3"))
 
