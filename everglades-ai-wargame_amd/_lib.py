@@ -32,6 +32,7 @@ EXPORTS = ["evg_default_tables", "evg_create", "evg_destroy", "evg_reset", "evg_
            "evg_league_clear", "evg_league_assign", "evg_league_importance", "evg_step_vs_league", "evg_step_vs_league_q",
            "evg_minimized_get_action", "evg_step_vs_policy_minimized_q", "evg_step_vs_league_minimized_q", "evg_minimized_qnet",
            "evg_step_minimized_q", "evg_step_league_minimized_q",
+           "evg_population_clear", "evg_population_assign", "evg_population_qnet",
            "evg_observe_seat",
            "evg_random_actions_seat", "evg_smart_state_seat", "evg_smart_state_compact", "evg_check_fault", "evg_rollout_vs_policy", "evg_fog_of_war",
            "evg_sightings", "evg_smart_state", "evg_smart_actions", "evg_smart_get_action", "evg_move_table", "evg_random_actions", "evg_rollout_random", "evg_rollout_policies",
@@ -129,6 +130,19 @@ class EvgLeague(C.Structure):
     ]
 
 
+class EvgPopulation(C.Structure):
+    """evg_population of include/evg.h: two teams of Minimized Q networks and the per-env assignment (device pointers the caller owns)."""
+    _fields_ = [
+        ("struct_size", C.c_uint32), ("h1", C.c_int32), ("final_relu", C.c_int32), ("num_members", C.c_int32 * 2), ("reserved", C.c_int32),
+        ("w1", (C.c_void_p * 16) * 2), ("b1", (C.c_void_p * 16) * 2), ("w2", (C.c_void_p * 16) * 2), ("b2", (C.c_void_p * 16) * 2),
+        ("member", C.c_void_p), ("counts", C.c_void_p), ("ctl", C.c_void_p),
+        ("index", C.c_void_p), ("first", C.c_void_p), ("count", C.c_void_p), ("hist", C.c_void_p), ("scratch_rows", C.c_int64),
+    ]
+
+
+POP_MAX_MEMBERS, POP_MAX_ROWS = 16, 1 << 24                   # EVG_POP_MAX_MEMBERS, EVG_POP_MAX_ROWS
+POP_S_BAD_MEMBER = 1                                          # EVG_POP_S_*
+POP_BINS, POP_BLOCK = 17, 256                                 # the bucket pass: 16 members + the bin of ids >= K; rows per workgroup
 LEAGUE_MAX_MEMBERS = 16
 LEAGUE_S_BAD_WEIGHTS, LEAGUE_S_BAD_ASSIGN = 1, 2              # EVG_LEAGUE_S_*
 ERR_ARG = -1          # EVG_ERR_ARG (= EVG_ERR_INVALID): a bad argument, e.g. a league descriptor out of range
@@ -233,6 +247,10 @@ def load(path=None):
     L.evg_step_minimized_q.argtypes = [vp, vp, C.c_float, C.c_float, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]
     L.evg_step_league_minimized_q.argtypes = [vp, vp, C.c_float, C.c_float, vp, lp, C.c_int, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]
     L.evg_minimized_qnet.argtypes = [vp, C.POINTER(EvgMiniQnet), C.c_int, C.c_int64, vp, vp, vp, vp]
+    pp = C.POINTER(EvgPopulation)
+    L.evg_population_clear.argtypes = [vp, pp, vp]
+    L.evg_population_assign.argtypes = [vp, pp, vp, vp, vp, vp]
+    L.evg_population_qnet.argtypes = [vp, pp, C.c_int, C.c_int64, C.c_int, vp, vp, vp, vp, vp]
     L.evg_random_actions_seat.argtypes = [vp, C.c_int, vp, vp]
     L.evg_smart_state_seat.argtypes = [vp, vp, vp, vp]
     L.evg_smart_state_compact.argtypes = [vp, C.c_int, vp, vp, vp, vp]

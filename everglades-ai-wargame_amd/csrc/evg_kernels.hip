@@ -79,6 +79,7 @@ namespace evg {
 #include "qnet_kernels.inc"     // the Smart_State Q network's forward pass (inference) on v_mfma_f32_16x16x4_f32
 #include "league_kernels.inc"   // the opponent league: clear, assign after an explicit reset, importance weights
 #include "minimized_qnet.inc"   // the Minimized agents' Q network's forward pass (59 -> h1 <= 128 -> 11) on v_mfma_f32_16x16x4_f32
+#include "population_kernels.inc"   // self-royale: per-env members drawn from a population, the bucket pass and the grouped Minimized forward
 
 // ---------------------------------------------------------------------------------------------
 // launchers

@@ -9,7 +9,7 @@ namespace evg {
 
 constexpr uint32_t PHILOX_M0 = 0xD2511F53u, PHILOX_M1 = 0xCD9E8D57u;
 constexpr uint32_t PHILOX_W0 = 0x9E3779B9u, PHILOX_W1 = 0xBB67AE85u;
-constexpr int RNG_COMBAT = 0, RNG_ACTION = 1, RNG_SWARM = 2, RNG_DELAY = 3, RNG_EXPLORE = 4, RNG_LEAGUE = 5;
+constexpr int RNG_COMBAT = 0, RNG_ACTION = 1, RNG_SWARM = 2, RNG_DELAY = 3, RNG_EXPLORE = 4, RNG_LEAGUE = 5, RNG_POPULATION = 6;
 
 // a ^ b ^ c in ONE instruction: gfx950's v_bitop3_b32 with truth table 0x96 (odd parity).  The compiler splits a three-input xor with a scalar operand into
 // two v_xor_b32 (6 VALU per Philox round where 4 suffice: 20 per block); the builtin takes the round key as the one scalar a VOP3 instruction may read.

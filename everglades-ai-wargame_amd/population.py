@@ -1,0 +1,209 @@
+"""QPopulation -- self-royale: a per-env Minimized Q network drawn from a population each episode (include/evg.h, evg_population).
+
+The device form of agents/Minimized/training_scripts/dqn_self_royale.py: each seat has a team of networks, `random.choice(team)` picks the member that
+plays an episode (:95-98), and only the members that played remember the game (:157-166) -- per ENV here: `member[e, p]` is the network of team p that
+plays env e's current episode, redrawn when the episode ends.
+
+    pop = env.q_population(team0, team1)                  # lists of whatever MinimizedQNet accepts; team1=None: team0 on both seats
+    q = pop(shared, swarm, out=q)                         # [N, 2, 34], [N, 2, 12, 13] -> [N, 2, 12, 11]: row [e, p] through team p's member[e, p]
+    env.step_q(q, eps, features=(shared, swarm), ...)     # the self-play turn, unchanged
+    pop.end_of_turn(history=ring[slot])                   # behind the step: history, per-member tally, the draw for the envs that finished
+    qt = pop.expanded(next_state_swarms, member, seat)    # the target networks on a sampled batch: [B, 12, 59], member [B] -> [B, 12, 11]
+
+Every Q row equals, bit for bit, what MinimizedQNet writes for it with that member's weights.  The parameters are read in place on every call.  No
+call synchronises with the host, and none allocates when `out` is given (expanded() keeps one id buffer per batch size).
+"""
+import ctypes as C
+
+import numpy as np
+
+from . import _lib
+from .qnet import MinimizedQNet
+
+
+class QPopulation(object):
+    OUT = _lib.MINI_QNET_OUT
+
+    def __init__(self, env, team0, team1=None, final_relu=None, max_rows=None):
+        """team0 / team1: 1..16 members each (QNetwork modules, nn.Sequentials or 4-tuples of tensors with final_relu=...), all of one hidden size and
+        one final_relu.  max_rows: the most rows a call evaluates (default 12 * num_envs: a batch of num_envs transitions in expanded()); the scratch
+        grows on demand beyond it, which allocates.  The constructor ends with clear(): create it after env.reset()."""
+        import torch
+        self.env, self.L = env, env.L
+        teams = [list(team0), list(team0 if team1 is None else team1)]
+        for t in teams:
+            if not 1 <= len(t) <= _lib.POP_MAX_MEMBERS:
+                raise ValueError("a team has 1..%d members, got %d" % (_lib.POP_MAX_MEMBERS, len(t)))
+        self.nets = [[MinimizedQNet(env, n, final_relu=final_relu) for n in t] for t in teams]
+        flat = [n for t in self.nets for n in t]
+        if any(n.pair for n in flat):
+            raise ValueError("a member is one network, not a pair")
+        if len({n.h1 for n in flat}) != 1 or len({n.final_relu for n in flat}) != 1:
+            raise ValueError("all members share the hidden size and the final ReLU (got h1 %s, final_relu %s)" % (
+                sorted({n.h1 for n in flat}), sorted({n.final_relu for n in flat})))
+        self.h1, self.final_relu = flat[0].h1, flat[0].final_relu
+        self.num_members = (len(teams[0]), len(teams[1]))
+        N = env.num_envs
+        with torch.cuda.device(env.device):
+            self.member = torch.zeros((N, 2), dtype=torch.uint8, device=env.device)              # the member of team p that plays env e
+            self.counts = torch.zeros((2, 16, 4), dtype=torch.int64, device=env.device)          # games, wins, ties, losses, from the member's seat
+            self._ctl = torch.zeros((2,), dtype=torch.int64, device=env.device)
+            self._bins = torch.zeros((2, 2, _lib.POP_BINS), dtype=torch.int32, device=env.device)   # first, count
+        d = _lib.EvgPopulation()
+        d.struct_size = C.sizeof(_lib.EvgPopulation)
+        d.h1, d.final_relu = self.h1, int(self.final_relu)
+        d.num_members[0], d.num_members[1] = self.num_members
+        d.member, d.counts, d.ctl = self.member.data_ptr(), self.counts.data_ptr(), self._ctl.data_ptr()
+        d.first, d.count = self._bins[0].data_ptr(), self._bins[1].data_ptr()
+        self._desc, self._ref = d, C.byref(d)
+        self._ids = {}
+        self._scratch(max(N, 12 * N) if max_rows is None else int(max_rows))
+        self.clear()
+
+    # ------------------------------------------------------------------ plumbing
+    def _scratch(self, rows):
+        import torch
+        rows = max(int(rows), 1)
+        with torch.cuda.device(self.env.device):
+            self._index = torch.zeros((2, rows), dtype=torch.int32, device=self.env.device)
+            self._hist = torch.zeros((2, _lib.POP_BINS, (rows + _lib.POP_BLOCK - 1) // _lib.POP_BLOCK), dtype=torch.int32, device=self.env.device)
+        self._desc.index, self._desc.hist, self._desc.scratch_rows = self._index.data_ptr(), self._hist.data_ptr(), rows
+
+    def _descriptor(self, rows):
+        if not 1 <= rows <= _lib.POP_MAX_ROWS:
+            raise ValueError("rows must lie in 1..2^24 (got %d)" % rows)
+        if rows > self._desc.scratch_rows:
+            self._scratch(rows)
+        d = self._desc
+        for p in range(2):
+            for m, net in enumerate(self.nets[p]):
+                ts, h1 = net._params(0)
+                if h1 != self.h1:
+                    raise ValueError("the hidden size of member %d of team %d changed from %d to %d" % (m, p, self.h1, h1))
+                d.w1[p][m], d.b1[p][m], d.w2[p][m], d.b2[p][m] = (t.data_ptr() for t in ts)
+        return self._ref
+
+    def _ids_of(self, member, lead, name="member"):
+        """member ids for rows of shape `lead`: a uint8 tensor of that shape, or of lead[:-1] (one id per transition, repeated over its rows)"""
+        import torch
+        if not isinstance(member, torch.Tensor) or member.dtype != torch.uint8 or member.device != self.env.device:
+            raise ValueError("%s must be a uint8 tensor on %s" % (name, self.env.device))
+        if tuple(member.shape) == tuple(lead):
+            if not member.is_contiguous():
+                raise ValueError("%s must be contiguous" % name)
+            return member
+        if len(lead) >= 2 and tuple(member.shape) == tuple(lead[:-1]):
+            buf = self._ids.get(tuple(lead))
+            if buf is None:
+                buf = self._ids[tuple(lead)] = torch.empty(tuple(lead), dtype=torch.uint8, device=self.env.device)
+            buf.copy_(member.unsqueeze(-1).expand(tuple(lead)))
+            return buf
+        raise ValueError("%s must have shape %s or %s, got %s" % (name, tuple(lead), tuple(lead[:-1]), tuple(member.shape)))
+
+    def _out(self, out, shape):
+        import torch
+        if out is None:
+            return torch.empty(shape, dtype=torch.float32, device=self.env.device)
+        return self.nets[0][0]._input(out, shape, "out")
+
+    def _launch(self, layout, rows, seat, member, in0, in1, out):
+        ref = self._descriptor(rows)
+        self.env._check(self.L.evg_population_qnet(self.env._h, ref, layout, rows, int(seat), C.c_void_p(member.data_ptr()), C.c_void_p(in0.data_ptr()),
+                                                   None if in1 is None else C.c_void_p(in1.data_ptr()), C.c_void_p(out.data_ptr()), self.env._stream()))
+        return out
+
+    # ------------------------------------------------------------------ the forward
+    def __call__(self, shared, swarm, out=None):
+        """Both seats' Q of every env from the compact features: shared [N, 2, 34], swarm [N, 2, 12, 13] -> [N, 2, 12, 11], row [e, p] through member
+        self.member[e, p] of team p (what step_q takes)."""
+        N = self.env.num_envs
+        chk = self.nets[0][0]._input
+        chk(shared, (N, 2, 34), "shared")
+        chk(swarm, (N, 2, 12, 13), "swarm")
+        out = self._out(out, (N, 2, 12, self.OUT))
+        return self._launch(_lib.QNET_COMPACT_SEATS, N, 0, self.member, shared, swarm, out)
+
+    def seat(self, shared, swarm, member, seat, out=None):
+        """One seat's compact features: shared [R, 34], swarm [R, 12, 13], member uint8 [R] -> [R, 12, 11], row r through member[r] of team `seat`."""
+        chk = self.nets[0][0]._input
+        if int(seat) not in (0, 1):
+            raise ValueError("seat must be 0 or 1")
+        R = shared.shape[0] if hasattr(shared, "shape") and len(shared.shape) == 2 else -1
+        chk(shared, (R, 34), "shared")
+        chk(swarm, (R, 12, 13), "swarm")
+        member = self._ids_of(member, (R,))
+        out = self._out(out, (R, 12, self.OUT))
+        return self._launch(_lib.QNET_COMPACT, R, seat, member, shared, swarm, out)
+
+    def expanded(self, x, member, seat, out=None):
+        """Expanded rows: x [..., 59] -> [..., 11], every row through its member of team `seat` (the target networks on SmartReplay.sample's
+        next_state_swarms [B, 12, 59]).  member: uint8 of x's leading shape, or without its last axis -- [B]: a transition's member for its 12 rows."""
+        import torch
+        if int(seat) not in (0, 1):
+            raise ValueError("seat must be 0 or 1")
+        if not isinstance(x, torch.Tensor) or x.dim() < 2 or x.shape[-1] != 59:
+            raise ValueError("x must be a float32 tensor [..., 59]")
+        self.nets[0][0]._input(x, tuple(x.shape), "x")
+        lead = tuple(x.shape[:-1])
+        member = self._ids_of(member, lead)
+        out = self._out(out, lead + (self.OUT,))
+        return self._launch(_lib.QNET_EXPANDED, x.numel() // 59, seat, member, x, None, out)
+
+    # ------------------------------------------------------------------ the assignment
+    def clear(self):
+        """Counters and status zeroed; both seats' members of every env drawn for the env's current episode.  Enqueued on the current stream."""
+        self.env._check(self.L.evg_population_clear(self.env._h, self._ref, self.env._stream()))
+
+    def _assign(self, mask, winner, history):
+        import torch
+        env, N = self.env, self.env.num_envs
+        if mask is not None:
+            if not (isinstance(mask, torch.Tensor) and mask.dtype == torch.uint8 and mask.is_contiguous() and mask.device == env.device):
+                mask = torch.as_tensor(mask, device=env.device).to(torch.uint8).contiguous()
+            if tuple(mask.shape) != (N,):
+                raise ValueError("mask must have one entry per env")
+        if winner is not None:
+            env._user(winner, (N,), torch.int8, "winner")
+        if history is not None:
+            env._user(history, (N, 2), torch.uint8, "history")
+        env._check(self.L.evg_population_assign(env._h, self._ref, env._ptr(mask), env._ptr(winner), env._ptr(history), env._stream()))
+
+    def end_of_turn(self, done=None, winner=None, history=None):
+        """Behind a step: for the envs of `done` (default: the env's own done buffer) -- `history` uint8 [N, 2], if given, receives the members that
+        played the finished episode; `winner` (default: the env's own winner buffer) is tallied for both seats' members; both are redrawn for the
+        episode that begins.  With auto_reset the step has already started that episode; without it, reset(done) first or use assign_after_reset()."""
+        self._assign(self.env.done if done is None else done, self.env.winner if winner is None else winner, history)
+
+    def assign_after_reset(self, mask=None):
+        """After an explicit env.reset(mask): draw the members of the envs of `mask` (None = all) for their new episode; nothing is tallied."""
+        self._assign(mask, None, None)
+
+    # ------------------------------------------------------------------ results
+    @property
+    def rows_per_member(self):
+        """int32 [2, 16] (a view): how many rows of the LAST forward went through each member of seat slot 0 / 1 (one-seat forwards fill slot 0)."""
+        return self._bins[1, :, :_lib.POP_MAX_MEMBERS]
+
+    def status(self):
+        """The sticky status bits (_lib.POP_S_BAD_MEMBER); synchronises."""
+        return int(self._ctl[0].item())
+
+    def check(self):
+        """Raise EvgError if a status bit is set; synchronises."""
+        st = self.status()
+        if st:
+            raise _lib.EvgError("population status %d: a member id was not below its team's size (its rows are zeros, its games untallied)" % st)
+
+    def state(self):
+        """The population's tensors as host arrays (np.savez-able); the networks are the caller's to save."""
+        return dict(num_members=np.asarray(self.num_members, np.int32), member=self.member.cpu().numpy(), counts=self.counts.cpu().numpy(),
+                    ctl=self._ctl.cpu().numpy())
+
+    def load_state(self, st):
+        """Restore state() onto a population created with the same team sizes (after env.restore())."""
+        import torch
+        if tuple(np.asarray(st["num_members"]).tolist()) != tuple(self.num_members):
+            raise ValueError("load_state: the saved population has other team sizes")
+        self.member.copy_(torch.as_tensor(np.asarray(st["member"], np.uint8)))
+        self.counts.copy_(torch.as_tensor(np.asarray(st["counts"], np.int64)))
+        self._ctl.copy_(torch.as_tensor(np.asarray(st["ctl"], np.int64)))

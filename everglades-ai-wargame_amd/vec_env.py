@@ -592,6 +592,12 @@ class EvergladesVecEnv(object):
         from .qnet import MinimizedQNet
         return MinimizedQNet(self, net, final_relu=final_relu)
 
+    def q_population(self, team0, team1=None, final_relu=None, max_rows=None):
+        """Self-royale (everglades_amd.QPopulation; evg_population): two teams of Minimized Q networks, a member per env and seat drawn each episode --
+        `pop(shared, swarm)` -> the q [N, 2, 12, 11] step_q() takes, `pop.end_of_turn()` behind the step.  team1=None plays team0 on both seats."""
+        from .population import QPopulation
+        return QPopulation(self, team0, team1, final_relu=final_relu, max_rows=max_rows)
+
     def smart_replay(self, capacity_turns, n_step=1, gamma=0.999, shaping="normalized_score", seats=0, episode_base=0):
         """The Smart_State learner's n-step replay memory on the device for this env (everglades_amd.SmartReplay: Multi_Step.NStepModule +
         DQNAgent.remember_game_state / end_of_episode / optimize_model's batch).  Storage is allocated once; record / sample / gather run without a host

@@ -45,7 +45,9 @@ extern "C" {
  *    the Minimized agents (agents/Minimized: a 59-h1-11 network, one Q per node): evg_minimized_get_action, evg_step_vs_policy_minimized_q,
  *    evg_step_vs_league_minimized_q, evg_minimized_qnet with its descriptor evg_mini_qnet -- added, no layout changed;
  *    Minimized self-play (a network on each seat): evg_step_minimized_q, evg_step_league_minimized_q (a league whose member q_member is the caller's
- *    second network) -- added, no layout changed */
+ *    second network) -- added, no layout changed;
+ *    self-royale (a per-env Minimized network drawn from a population each episode): evg_population_clear / evg_population_assign /
+ *    evg_population_qnet with their descriptor evg_population -- added, no layout changed */
 /* 6: evg_smart_get_action (DQNAgent.get_action with epsilon > 0), evg_step_vs_policy_smart (the learner-seat turn that also writes the Smart_State
  *    features), evg_get_run_state / evg_set_run_state (agent objects, returns, win counters: checkpoint / resume); reward / score buffers need 8-byte
  *    alignment only (5 asked 16 of every buffer)
@@ -796,6 +798,67 @@ typedef struct evg_mini_qnet {
 } evg_mini_qnet;
 EVG_API int evg_minimized_qnet(evg_handle* h, const evg_mini_qnet* net, int layout, int64_t rows, const float* in0, const float* in1, float* q_out,
                                void* stream);
+
+/* ---- Self-royale: a per-env Minimized Q network drawn from a population each episode ---------------------------------------------------------------------
+ * agents/Minimized/training_scripts/dqn_self_royale.py (:42-62, :95-98, :157-166): each seat has a team of networks, random.choice(team) picks the member
+ * that plays an episode, and only the members that played remember the game.  Per ENV here: member[e][p] is the network of team p that plays env e's
+ * current episode.  Added under ABI 7: three functions and one descriptor struct; nothing that existed changed, and no step kernel knows about it -- the
+ * forward writes the q [N][2][12][11] that evg_step_minimized_q takes, the assignment is a side kernel enqueued behind the step.
+ *
+ * A population is two teams of K[p] = num_members[p] networks (1..EVG_POP_MAX_MEMBERS each) of one hidden size h1, member m of team p being the weight
+ * set {w1[p][m], b1[p][m], w2[p][m], b2[p][m]} in evg_mini_qnet's layout (read in place on every call).  Storage is caller-owned device memory
+ * (everglades_amd.QPopulation allocates it):
+ *   member   uint8 [N][2]          the member of team p that plays env e in its current episode
+ *   counts   uint64 [2][16][4]     {games, wins, ties, losses} of member m of team p, seen from seat p
+ *   ctl      uint64 [2]            {status bits EVG_POP_S_* (sticky until evg_population_clear), reserved}
+ *   index    int32 [2][scratch_rows], first / count int32 [2][17], hist int32 [2][17][ceil(scratch_rows / 256)]: the bucket pass's scratch and results
+ *                                  (below); scratch_rows >= the rows of every evg_population_qnet call
+ * ASSIGNMENT.  The member of (env e, seat p) for episode k is random.choice(team) restated on a keyed draw (domain 6):
+ * member = (w * K[p]) >> 32 with w = word .x of the Philox block (domain 6, block 0, turn 0, node 0, player p, group 0, episode k, global env id).  A team
+ * of one draws nothing observable: its member is 0.  Keyed-Philox handles only.
+ * FORWARD.  evg_population_qnet is evg_minimized_qnet with the weight set chosen per row; every Q row equals, bit for bit, what evg_minimized_qnet
+ * writes for that row with the weights of team[seat][member[row]].  It first buckets the rows by member id -- a stable counting sort without global
+ * atomics: index[s][first[s][m] .. + count[s][m]) lists the rows of member m in ascending order, bin 16 the rows whose id is >= K -- and then runs one
+ * workgroup set per (seat, member) over its list.  A row with an id >= K gets zeros and sets EVG_POP_S_BAD_MEMBER; such an id never selects weights. */
+#define EVG_POP_MAX_MEMBERS 16
+#define EVG_POP_MAX_ROWS (1 << 24)
+enum { EVG_POP_S_BAD_MEMBER = 1 };
+typedef struct evg_population {
+    uint32_t struct_size;                       /* sizeof(evg_population)                          */
+    int32_t h1;                                 /* hidden size of every member, 1..128             */
+    int32_t final_relu;                         /* 0 / 1: the ReLU (NaN kept) on the output layer  */
+    int32_t num_members[2];                     /* K[p], 1..16                                     */
+    int32_t reserved;                           /* 0                                               */
+    const float* w1[2][EVG_POP_MAX_MEMBERS];    /* entries >= K[p] are ignored                     */
+    const float* b1[2][EVG_POP_MAX_MEMBERS];
+    const float* w2[2][EVG_POP_MAX_MEMBERS];
+    const float* b2[2][EVG_POP_MAX_MEMBERS];
+    uint8_t* member;
+    unsigned long long* counts;
+    unsigned long long* ctl;
+    int32_t* index;
+    int32_t* first;
+    int32_t* count;
+    int32_t* hist;
+    int64_t scratch_rows;
+} evg_population;
+/* Counts and status are zeroed and both seats' members of every env are drawn for the env's current episode. */
+EVG_API int evg_population_clear(evg_handle* h, const evg_population* pop, void* stream);
+/* For every env of mask (device uint8 [N]; NULL = all), in this order: history_out (uint8 [N][2] or NULL) receives the members that played, i.e. member
+ * as it stands; winner (int8 [N], EVG_WINNER_*, or NULL) is tallied for both seats' members, each from its own seat (P0 / P1 = that seat's win, TIE, else
+ * a loss; EVG_WINNER_NONE tallies nothing, a stored id >= K tallies nothing and sets EVG_POP_S_BAD_MEMBER); both seats' members are drawn for the episode
+ * the handle's episode counter names when the call runs (evg_league_assign's convention).  With auto_reset call it behind every step with the step's
+ * done_out as mask and its winner_out; after an explicit evg_reset(mask) with that mask and winner = NULL. */
+EVG_API int evg_population_assign(evg_handle* h, const evg_population* pop, const uint8_t* mask, const int8_t* winner, uint8_t* history_out, void* stream);
+/* The forward of `rows` rows (1..2^24, <= scratch_rows), layouts and tensors as evg_minimized_qnet:
+ *   EVG_QNET_COMPACT_SEATS  member uint8 [rows][2] (e.g. pop->member itself); seat ignored; row [r][p] through team p
+ *   EVG_QNET_COMPACT        member uint8 [rows]; every row through team `seat`
+ *   EVG_QNET_EXPANDED       member uint8 [rows]; every row through team `seat` (the target networks on a sampled batch)
+ * Four launches on `stream` (three of the bucket pass, one forward sized for the worst case: the counts stay on the device), no synchronisation, nothing
+ * allocated.  Refused with EVG_ERR_INVALID (nothing launched): what evg_minimized_qnet refuses, struct_size, num_members outside 1..16, a NULL buffer of
+ * the descriptor, a NULL member, seat outside 0..1, rows outside 1..2^24 or above scratch_rows. */
+EVG_API int evg_population_qnet(evg_handle* h, const evg_population* pop, int layout, int64_t rows, int seat, const uint8_t* member, const float* in0,
+                                const float* in1, float* q_out, void* stream);
 
 #ifdef __cplusplus
 }
