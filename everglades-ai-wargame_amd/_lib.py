@@ -33,6 +33,7 @@ EXPORTS = ["evg_default_tables", "evg_create", "evg_destroy", "evg_reset", "evg_
            "evg_minimized_get_action", "evg_step_vs_policy_minimized_q", "evg_step_vs_league_minimized_q", "evg_minimized_qnet",
            "evg_step_minimized_q", "evg_step_league_minimized_q",
            "evg_population_clear", "evg_population_assign", "evg_population_qnet",
+           "evg_smart_population_clear", "evg_smart_population_assign", "evg_smart_population_qnet",
            "evg_observe_seat",
            "evg_random_actions_seat", "evg_smart_state_seat", "evg_smart_state_compact", "evg_check_fault", "evg_rollout_vs_policy", "evg_fog_of_war",
            "evg_sightings", "evg_smart_state", "evg_smart_actions", "evg_smart_get_action", "evg_move_table", "evg_random_actions", "evg_rollout_random", "evg_rollout_policies",
@@ -135,6 +136,17 @@ class EvgPopulation(C.Structure):
     _fields_ = [
         ("struct_size", C.c_uint32), ("h1", C.c_int32), ("final_relu", C.c_int32), ("num_members", C.c_int32 * 2), ("reserved", C.c_int32),
         ("w1", (C.c_void_p * 16) * 2), ("b1", (C.c_void_p * 16) * 2), ("w2", (C.c_void_p * 16) * 2), ("b2", (C.c_void_p * 16) * 2),
+        ("member", C.c_void_p), ("counts", C.c_void_p), ("ctl", C.c_void_p),
+        ("index", C.c_void_p), ("first", C.c_void_p), ("count", C.c_void_p), ("hist", C.c_void_p), ("scratch_rows", C.c_int64),
+    ]
+
+
+class EvgSmartPopulation(C.Structure):
+    """evg_smart_population of include/evg.h: two teams of Smart_State Q networks and the per-env assignment (device pointers the caller owns)."""
+    _fields_ = [
+        ("struct_size", C.c_uint32), ("h1", C.c_int32), ("h2", C.c_int32), ("final_relu", C.c_int32), ("num_members", C.c_int32 * 2),
+        ("w1", (C.c_void_p * 16) * 2), ("b1", (C.c_void_p * 16) * 2), ("w2", (C.c_void_p * 16) * 2), ("b2", (C.c_void_p * 16) * 2),
+        ("w3", (C.c_void_p * 16) * 2), ("b3", (C.c_void_p * 16) * 2),
         ("member", C.c_void_p), ("counts", C.c_void_p), ("ctl", C.c_void_p),
         ("index", C.c_void_p), ("first", C.c_void_p), ("count", C.c_void_p), ("hist", C.c_void_p), ("scratch_rows", C.c_int64),
     ]
@@ -251,6 +263,10 @@ def load(path=None):
     L.evg_population_clear.argtypes = [vp, pp, vp]
     L.evg_population_assign.argtypes = [vp, pp, vp, vp, vp, vp]
     L.evg_population_qnet.argtypes = [vp, pp, C.c_int, C.c_int64, C.c_int, vp, vp, vp, vp, vp]
+    sp = C.POINTER(EvgSmartPopulation)
+    L.evg_smart_population_clear.argtypes = [vp, sp, vp]
+    L.evg_smart_population_assign.argtypes = [vp, sp, vp, vp, vp, vp]
+    L.evg_smart_population_qnet.argtypes = [vp, sp, C.c_int, C.c_int64, C.c_int, vp, vp, vp, vp, vp]
     L.evg_random_actions_seat.argtypes = [vp, C.c_int, vp, vp]
     L.evg_smart_state_seat.argtypes = [vp, vp, vp, vp]
     L.evg_smart_state_compact.argtypes = [vp, C.c_int, vp, vp, vp, vp]

@@ -1268,6 +1268,72 @@ int evg_population_qnet(evg_handle* h, const evg_population* pop, int layout, in
                                                               q_out, h->caps.cus, stream));
 } catch (...) { return on_exception(); }
 
+// ---- Smart_State self-royale (include/evg.h: evg_smart_population_clear / _assign / _qnet) ----
+static int check_smart_population(const evg_handle* h, const evg_smart_population* pop, bool forward) {
+    if (!h || !pop) return fail(EVG_ERR_INVALID, "null handle or population descriptor");
+    if (pop->struct_size != sizeof(evg_smart_population))
+        return fail(EVG_ERR_INVALID, "smart population: struct_size %u != sizeof(evg_smart_population) %zu", pop->struct_size, sizeof(evg_smart_population));
+    if (pop->h1 < 1 || pop->h1 > EVG_QNET_MAX_HIDDEN || pop->h2 < 1 || pop->h2 > EVG_QNET_MAX_HIDDEN)
+        return fail(EVG_ERR_INVALID, "smart population: hidden sizes must lie in 1..%d (got %d, %d)", EVG_QNET_MAX_HIDDEN, pop->h1, pop->h2);
+    if (pop->final_relu != 0 && pop->final_relu != 1) return fail(EVG_ERR_INVALID, "smart population: final_relu must be 0 or 1 (got %d)", pop->final_relu);
+    for (int p = 0; p < 2; ++p)
+        if (pop->num_members[p] < 1 || pop->num_members[p] > EVG_POP_MAX_MEMBERS)
+            return fail(EVG_ERR_INVALID, "smart population: num_members[%d] must lie in 1..%d (got %d)", p, EVG_POP_MAX_MEMBERS, pop->num_members[p]);
+    if (!pop->member || !pop->counts || !pop->ctl) return fail(EVG_ERR_INVALID, "smart population: member, counts and ctl are required");
+    EVG_NEED_ALIGNED8(pop->counts); EVG_NEED_ALIGNED8(pop->ctl);
+    if (reinterpret_cast<uintptr_t>(pop->member) % 2) return fail(EVG_ERR_INVALID, "smart population: member must be 2-byte aligned");
+    if (!forward) return EVG_OK;
+    if (!pop->index || !pop->first || !pop->count || !pop->hist) return fail(EVG_ERR_INVALID, "smart population: index, first, count and hist are required");
+    if (reinterpret_cast<uintptr_t>(pop->index) % 4 || reinterpret_cast<uintptr_t>(pop->first) % 4 || reinterpret_cast<uintptr_t>(pop->count) % 4 ||
+        reinterpret_cast<uintptr_t>(pop->hist) % 4)
+        return fail(EVG_ERR_INVALID, "smart population: index, first, count and hist must be 4-byte aligned");
+    for (int p = 0; p < 2; ++p)
+        for (int m = 0; m < pop->num_members[p]; ++m) {
+            const float* w[6] = {pop->w1[p][m], pop->b1[p][m], pop->w2[p][m], pop->b2[p][m], pop->w3[p][m], pop->b3[p][m]};
+            static const char* names[6] = {"w1", "b1", "w2", "b2", "w3", "b3"};
+            for (int i = 0; i < 6; ++i) {
+                if (!w[i]) return fail(EVG_ERR_INVALID, "smart population: %s[%d][%d] is NULL", names[i], p, m);
+                if (misaligned16(w[i]))
+                    return fail(EVG_ERR_INVALID, "smart population: %s[%d][%d] must be 16-byte aligned (got %p)", names[i], p, m, (const void*)w[i]);
+            }
+        }
+    return EVG_OK;
+}
+
+int evg_smart_population_clear(evg_handle* h, const evg_smart_population* pop, void* stream) try {
+    { const int rc = check_smart_population(h, pop, false); if (rc) return rc; }
+    if (const int rc = check_keyed_philox(h, "evg_smart_population_clear", " (the member draw is keyed)")) return rc;
+    EVG_ON_DEVICE(h);
+    return launched("smart population clear", launch_smart_population_clear(h->S, *pop, stream));
+} catch (...) { return on_exception(); }
+
+int evg_smart_population_assign(evg_handle* h, const evg_smart_population* pop, const uint8_t* mask, const int8_t* winner, uint8_t* history_out,
+                                void* stream) try {
+    { const int rc = check_smart_population(h, pop, false); if (rc) return rc; }
+    if (const int rc = check_keyed_philox(h, "evg_smart_population_assign", " (the member draw is keyed)")) return rc;
+    if (reinterpret_cast<uintptr_t>(history_out) % 2) return fail(EVG_ERR_INVALID, "smart population: history_out must be 2-byte aligned");
+    EVG_ON_DEVICE(h);
+    return launched("smart population assign", launch_smart_population_assign(h->S, *pop, mask, winner, history_out, stream));
+} catch (...) { return on_exception(); }
+
+int evg_smart_population_qnet(evg_handle* h, const evg_smart_population* pop, int layout, int64_t rows, int seat, const uint8_t* member, const float* in0,
+                              const float* in1, float* q_out, void* stream) try {
+    { const int rc = check_smart_population(h, pop, true); if (rc) return rc; }
+    if (layout != EVG_QNET_COMPACT && layout != EVG_QNET_COMPACT_SEATS && layout != EVG_QNET_EXPANDED)
+        return fail(EVG_ERR_INVALID, "smart population qnet: unknown layout %d", layout);
+    if (layout != EVG_QNET_COMPACT_SEATS && (seat < 0 || seat > 1)) return fail(EVG_ERR_INVALID, "smart population qnet: seat must be 0 or 1 (got %d)", seat);
+    if (rows < 1 || rows > EVG_POP_MAX_ROWS) return fail(EVG_ERR_INVALID, "smart population qnet: rows must lie in 1..2^24 (got %lld)", (long long)rows);
+    if (rows > pop->scratch_rows)
+        return fail(EVG_ERR_INVALID, "smart population qnet: %lld rows, but the descriptor's scratch holds %lld", (long long)rows,
+                    (long long)pop->scratch_rows);
+    if (!member || !in0 || !q_out || (layout != EVG_QNET_EXPANDED && !in1))
+        return fail(EVG_ERR_INVALID, "smart population qnet: member, in0, q_out and (compact layouts) in1 are required");
+    EVG_NEED_ALIGNED16(in0); EVG_NEED_ALIGNED16(in1); EVG_NEED_ALIGNED16(q_out);
+    EVG_ON_DEVICE(h);
+    return launched("smart population qnet", launch_smart_population_qnet(*pop, layout, (long long)rows, layout == EVG_QNET_COMPACT_SEATS ? 0 : seat,
+                                                                          member, in0, in1, q_out, h->caps.cus, stream));
+} catch (...) { return on_exception(); }
+
 void evg_move_table(int32_t* table /* [11][5] */) {
     // agents/Smart_State/Move_Translation.py:3-97: node reached from (0-indexed) node n0 in direction 0 left, 1 right, 2 up, 3 down, 4 stay
     static const int32_t T[5][11] = {{1, 1, 3, 1, 2, 3, 4, 5, 6, 7, 11}, {1, 5, 6, 7, 8, 9, 10, 11, 9, 11, 11}, {2, 2, 2, 3, 5, 6, 7, 8, 8, 9, 8},

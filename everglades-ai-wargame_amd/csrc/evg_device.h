@@ -251,5 +251,11 @@ int launch_population_clear(const DevState& S, const evg_population& pop, void* 
 int launch_population_assign(const DevState& S, const evg_population& pop, const uint8_t* mask, const int8_t* winner, uint8_t* history, void* stream);
 int launch_population_qnet(const evg_population& pop, int layout, long long rows, int seat, const uint8_t* member, const float* in0, const float* in1,
                            float* q_out, int num_cu, void* stream);
+// Smart_State self-royale (population_kernels.inc): the same assignment kernels, the grouped evg_qnet_kernel
+int launch_smart_population_clear(const DevState& S, const evg_smart_population& pop, void* stream);
+int launch_smart_population_assign(const DevState& S, const evg_smart_population& pop, const uint8_t* mask, const int8_t* winner, uint8_t* history,
+                                   void* stream);
+int launch_smart_population_qnet(const evg_smart_population& pop, int layout, long long rows, int seat, const uint8_t* member, const float* in0,
+                                 const float* in1, float* q_out, int num_cu, void* stream);
 
 }  // namespace evg

@@ -13,6 +13,8 @@
 //                                   16) get zeros in q_out and set EVG_POP_S_BAD_MEMBER; they are in no member's list
 //   evg_mini_qnet_pop_kernel<EXPANDED>   evg_mini_qnet_kernel with a workgroup belonging to one (seat slot, member): it stages that member's weights once
 //                                   and runs the shared body over the member's list, reading rows through it and writing Q to their original positions
+//   evg_qnet_pop_kernel<EXPANDED>   the same for the Smart_State network (evg_smart_population): evg_qnet_kernel's body (qnet_body.inc) over a member's
+//                                   list.  Its assignment and bucket pass are the kernels above, unchanged (row_floats 5 / 60)
 //
 // The draw (RNG domain 6 = RNG_POPULATION, DESIGN.md section 4; tests/population_model.py is the host statement): member = mulhi32(w, K) with w = word .x
 // of the block (domain 6, block 0, turn 0, node 0, player = seat, group 0, episode, env id) -- the form the combat draw uses; K = 1 draws nothing.
@@ -213,6 +215,45 @@ __global__ void __launch_bounds__(64 * QN_WAVES) evg_mini_qnet_pop_kernel(MiniPo
 #undef MQ_GROUPED
 }
 
+// ---- the grouped Smart_State forward (evg_smart_population): evg_qnet_kernel with a workgroup belonging to one (seat slot, member)
+struct SmartPopArgs {
+    QnetArgs q;                                       // (its `set` is not read: the sets are below)
+    QnetSet set[2][EVG_POP_MAX_MEMBERS];              // [seat slot][member]
+    const int32_t* index;
+    const int32_t* first;
+    const int32_t* count;
+    int32_t num0, num1, ky;                           // members per seat slot; blockIdx.y = slot * ky + member
+};
+
+template <bool EXPANDED>
+__global__ void __launch_bounds__(64 * QN_WAVES) evg_qnet_pop_kernel(SmartPopArgs p) {
+    __shared__ float fixed[QN_FIXED];
+    __shared__ __attribute__((aligned(16))) float lds[QN_UNION];
+    const int slot = (int)blockIdx.y / p.ky, member = (int)blockIdx.y - slot * p.ky;
+    if (member >= (slot ? p.num1 : p.num0)) return;
+    // evg_mini_qnet_pop_kernel's prologue: a member's rows get its share of a grid sized for the worst case, the other workgroups leave here, uniformly,
+    // before any weight is staged
+    const long long rows = p.q.rows;
+    long long cnt = p.count[slot * POP_BINS + member];
+    cnt = cnt < rows ? cnt : rows;
+    if (cnt <= 0) return;
+    long long first = p.first[slot * POP_BINS + member];
+    first = first < 0 ? 0 : (first < rows - cnt ? first : rows - cnt);
+    const long long need = (cnt + 16 * QN_WAVES - 1) / (16 * QN_WAVES);
+    long long live = ((long long)gridDim.x * cnt + rows - 1) / rows;
+    live = live < need ? live : need;
+    if ((long long)blockIdx.x >= live) return;
+    const QnetArgs& a = p.q;
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int seat = slot;
+    const QnetSet W = p.set[slot][member];
+    const int* const list = p.index + (long long)slot * rows + first;
+    const long long list_rows = cnt, list_stride = live * QN_WAVES;
+#define QN_GROUPED 1
+#include "qnet_body.inc"
+#undef QN_GROUPED
+}
+
 static PopArgs pop_args(const evg_population& pop) { return PopArgs{pop.member, pop.counts, pop.ctl, pop.num_members[0], pop.num_members[1]}; }
 
 int launch_population_clear(const DevState& S, const evg_population& pop, void* stream) {
@@ -264,5 +305,62 @@ int launch_population_qnet(const evg_population& pop, int layout, long long rows
         hipLaunchKernelGGL(evg_mini_qnet_pop_kernel<true>, grid, dim3(64 * QN_WAVES), 0, s, p);
     else
         hipLaunchKernelGGL(evg_mini_qnet_pop_kernel<false>, grid, dim3(64 * QN_WAVES), 0, s, p);
+    return (int)hipGetLastError();
+}
+
+static PopArgs pop_args(const evg_smart_population& pop) { return PopArgs{pop.member, pop.counts, pop.ctl, pop.num_members[0], pop.num_members[1]}; }
+
+// the assignment of a Smart_State population: the same two kernels through the same PopArgs, hence the same draws
+int launch_smart_population_clear(const DevState& S, const evg_smart_population& pop, void* stream) {
+    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+    if (hipMemsetAsync(pop.counts, 0, sizeof(unsigned long long) * 2 * EVG_POP_MAX_MEMBERS * 4, s) != hipSuccess) return (int)hipGetLastError();
+    if (hipMemsetAsync(pop.ctl, 0, sizeof(unsigned long long) * 2, s) != hipSuccess) return (int)hipGetLastError();
+    hipLaunchKernelGGL(evg_population_clear_kernel, dim3((S.N + 255) / 256), dim3(256), 0, s, S, pop_args(pop));
+    return (int)hipGetLastError();
+}
+
+int launch_smart_population_assign(const DevState& S, const evg_smart_population& pop, const uint8_t* mask, const int8_t* winner, uint8_t* history,
+                                   void* stream) {
+    hipLaunchKernelGGL(evg_population_assign_kernel, dim3((S.N + 255) / 256), dim3(256), 0, reinterpret_cast<hipStream_t>(stream), S, pop_args(pop), mask,
+                       winner, history);
+    return (int)hipGetLastError();
+}
+
+int launch_smart_population_qnet(const evg_smart_population& pop, int layout, long long rows, int seat, const uint8_t* member, const float* in0,
+                                 const float* in1, float* q_out, int num_cu, void* stream) {
+    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+    const int S = layout == EVG_QNET_COMPACT_SEATS ? 2 : 1;
+    const int team[2] = {S == 2 ? 0 : seat, 1};      // the team that plays seat slot 0 / 1
+    PopBucket b;
+    b.member = member; b.index = pop.index; b.first = pop.first; b.count = pop.count; b.hist = pop.hist; b.ctl = pop.ctl; b.out = q_out;
+    b.rows = (int32_t)rows; b.S = S; b.nb = (int32_t)((rows + POP_BLOCK - 1) / POP_BLOCK);
+    b.row_floats = layout == EVG_QNET_EXPANDED ? QN_OUT : 12 * QN_OUT;
+    b.num0 = pop.num_members[team[0]]; b.num1 = pop.num_members[team[1]];
+    hipLaunchKernelGGL(evg_population_hist_kernel, dim3((unsigned)b.nb, (unsigned)S), dim3(POP_BLOCK), 0, s, b);
+    hipLaunchKernelGGL(evg_population_scan_kernel, dim3((unsigned)S), dim3(256), 0, s, b);
+    hipLaunchKernelGGL(evg_population_scatter_kernel, dim3((unsigned)b.nb, (unsigned)S), dim3(POP_BLOCK), 0, s, b);
+
+    SmartPopArgs p;
+    for (int t = 0; t < 2; ++t) p.q.set[t] = QnetSet{nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
+    p.q.h1 = pop.h1; p.q.h2 = pop.h2; p.q.final_relu = pop.final_relu; p.q.num_seats = S; p.q.rows = rows; p.q.in0 = in0; p.q.in1 = in1; p.q.out = q_out;
+    for (int t = 0; t < 2; ++t)
+        for (int m = 0; m < EVG_POP_MAX_MEMBERS; ++m) {
+            const int q = team[t];
+            p.set[t][m] = m < pop.num_members[q] ? QnetSet{pop.w1[q][m], pop.b1[q][m], pop.w2[q][m], pop.b2[q][m], pop.w3[q][m], pop.b3[q][m]}
+                                                 : QnetSet{nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
+        }
+    p.index = pop.index; p.first = pop.first; p.count = pop.count;
+    p.num0 = b.num0; p.num1 = b.num1;
+    p.ky = S == 2 && b.num1 > b.num0 ? b.num1 : b.num0;
+    // launch_smart_qnet's grid (two workgroups per CU resident) per seat slot, times the members: each member's rows use their share of it
+    const long long groups = (rows + 15) / 16;
+    long long blocks = (groups + QN_WAVES - 1) / QN_WAVES;
+    const long long cap = 2LL * (num_cu > 0 ? num_cu : 256);
+    if (blocks > cap) blocks = cap;
+    const dim3 grid((unsigned)blocks, (unsigned)(S * p.ky));
+    if (layout == EVG_QNET_EXPANDED)
+        hipLaunchKernelGGL(evg_qnet_pop_kernel<true>, grid, dim3(64 * QN_WAVES), 0, s, p);
+    else
+        hipLaunchKernelGGL(evg_qnet_pop_kernel<false>, grid, dim3(64 * QN_WAVES), 0, s, p);
     return (int)hipGetLastError();
 }

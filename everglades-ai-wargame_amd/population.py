@@ -1,4 +1,5 @@
-"""QPopulation -- self-royale: a per-env Minimized Q network drawn from a population each episode (include/evg.h, evg_population).
+"""QPopulation / SmartQPopulation -- self-royale: a per-env Q network drawn from a population each episode (include/evg.h, evg_population for the
+Minimized 59-h1-11 network, evg_smart_population for the Smart_State 59-h1-h2-5 network; one surface, SmartQPopulation below).
 
 The device form of agents/Minimized/training_scripts/dqn_self_royale.py: each seat has a team of networks, `random.choice(team)` picks the member that
 plays an episode (:95-98), and only the members that played remember the game (:157-166) -- per ENV here: `member[e, p]` is the network of team p that
@@ -18,11 +19,24 @@ import ctypes as C
 import numpy as np
 
 from . import _lib
-from .qnet import MinimizedQNet
+from .qnet import MinimizedQNet, SmartQNet
 
 
 class QPopulation(object):
     OUT = _lib.MINI_QNET_OUT
+    # what a population of another network family changes (SmartQPopulation): the evaluator of a member, the descriptor, its entry points' prefix,
+    # the descriptor's weight tables in the order of the evaluator's _params(), and how the hidden sizes are named
+    _NET, _DESC, _FN, _PARAMS, _SIZE_NAME = MinimizedQNet, _lib.EvgPopulation, "evg_population", ("w1", "b1", "w2", "b2"), "h1"
+
+    @staticmethod
+    def _size(net):
+        """the hidden size(s) of a member's evaluator, as its _params() reports them"""
+        return net.h1
+
+    def _set_size(self, size, desc=None):
+        self.h1 = size
+        if desc is not None:
+            desc.h1 = size
 
     def __init__(self, env, team0, team1=None, final_relu=None, max_rows=None):
         """team0 / team1: 1..16 members each (QNetwork modules, nn.Sequentials or 4-tuples of tensors with final_relu=...), all of one hidden size and
@@ -34,14 +48,15 @@ class QPopulation(object):
         for t in teams:
             if not 1 <= len(t) <= _lib.POP_MAX_MEMBERS:
                 raise ValueError("a team has 1..%d members, got %d" % (_lib.POP_MAX_MEMBERS, len(t)))
-        self.nets = [[MinimizedQNet(env, n, final_relu=final_relu) for n in t] for t in teams]
+        self.nets = [[self._NET(env, n, final_relu=final_relu) for n in t] for t in teams]
         flat = [n for t in self.nets for n in t]
         if any(n.pair for n in flat):
             raise ValueError("a member is one network, not a pair")
-        if len({n.h1 for n in flat}) != 1 or len({n.final_relu for n in flat}) != 1:
-            raise ValueError("all members share the hidden size and the final ReLU (got h1 %s, final_relu %s)" % (
-                sorted({n.h1 for n in flat}), sorted({n.final_relu for n in flat})))
-        self.h1, self.final_relu = flat[0].h1, flat[0].final_relu
+        if len({self._size(n) for n in flat}) != 1 or len({n.final_relu for n in flat}) != 1:
+            raise ValueError("all members share the hidden size and the final ReLU (got %s %s, final_relu %s)" % (
+                self._SIZE_NAME, sorted({self._size(n) for n in flat}), sorted({n.final_relu for n in flat})))
+        self._hidden, self.final_relu = self._size(flat[0]), flat[0].final_relu
+        self._set_size(self._hidden)
         self.num_members = (len(teams[0]), len(teams[1]))
         N = env.num_envs
         with torch.cuda.device(env.device):
@@ -49,9 +64,10 @@ class QPopulation(object):
             self.counts = torch.zeros((2, 16, 4), dtype=torch.int64, device=env.device)          # games, wins, ties, losses, from the member's seat
             self._ctl = torch.zeros((2,), dtype=torch.int64, device=env.device)
             self._bins = torch.zeros((2, 2, _lib.POP_BINS), dtype=torch.int32, device=env.device)   # first, count
-        d = _lib.EvgPopulation()
-        d.struct_size = C.sizeof(_lib.EvgPopulation)
-        d.h1, d.final_relu = self.h1, int(self.final_relu)
+        d = self._DESC()
+        d.struct_size = C.sizeof(self._DESC)
+        self._set_size(self._hidden, d)
+        d.final_relu = int(self.final_relu)
         d.num_members[0], d.num_members[1] = self.num_members
         d.member, d.counts, d.ctl = self.member.data_ptr(), self.counts.data_ptr(), self._ctl.data_ptr()
         d.first, d.count = self._bins[0].data_ptr(), self._bins[1].data_ptr()
@@ -77,10 +93,11 @@ class QPopulation(object):
         d = self._desc
         for p in range(2):
             for m, net in enumerate(self.nets[p]):
-                ts, h1 = net._params(0)
-                if h1 != self.h1:
-                    raise ValueError("the hidden size of member %d of team %d changed from %d to %d" % (m, p, self.h1, h1))
-                d.w1[p][m], d.b1[p][m], d.w2[p][m], d.b2[p][m] = (t.data_ptr() for t in ts)
+                ts, size = net._params(0)
+                if size != self._hidden:
+                    raise ValueError("the hidden size of member %d of team %d changed from %s to %s" % (m, p, self._hidden, size))
+                for name, t in zip(self._PARAMS, ts):
+                    getattr(d, name)[p][m] = t.data_ptr()
         return self._ref
 
     def _ids_of(self, member, lead, name="member"):
@@ -108,8 +125,9 @@ class QPopulation(object):
 
     def _launch(self, layout, rows, seat, member, in0, in1, out):
         ref = self._descriptor(rows)
-        self.env._check(self.L.evg_population_qnet(self.env._h, ref, layout, rows, int(seat), C.c_void_p(member.data_ptr()), C.c_void_p(in0.data_ptr()),
-                                                   None if in1 is None else C.c_void_p(in1.data_ptr()), C.c_void_p(out.data_ptr()), self.env._stream()))
+        self.env._check(getattr(self.L, self._FN + "_qnet")(self.env._h, ref, layout, rows, int(seat), C.c_void_p(member.data_ptr()),
+                                                            C.c_void_p(in0.data_ptr()), None if in1 is None else C.c_void_p(in1.data_ptr()),
+                                                            C.c_void_p(out.data_ptr()), self.env._stream()))
         return out
 
     # ------------------------------------------------------------------ the forward
@@ -152,7 +170,7 @@ class QPopulation(object):
     # ------------------------------------------------------------------ the assignment
     def clear(self):
         """Counters and status zeroed; both seats' members of every env drawn for the env's current episode.  Enqueued on the current stream."""
-        self.env._check(self.L.evg_population_clear(self.env._h, self._ref, self.env._stream()))
+        self.env._check(getattr(self.L, self._FN + "_clear")(self.env._h, self._ref, self.env._stream()))
 
     def _assign(self, mask, winner, history):
         import torch
@@ -166,7 +184,7 @@ class QPopulation(object):
             env._user(winner, (N,), torch.int8, "winner")
         if history is not None:
             env._user(history, (N, 2), torch.uint8, "history")
-        env._check(self.L.evg_population_assign(env._h, self._ref, env._ptr(mask), env._ptr(winner), env._ptr(history), env._stream()))
+        env._check(getattr(self.L, self._FN + "_assign")(env._h, self._ref, env._ptr(mask), env._ptr(winner), env._ptr(history), env._stream()))
 
     def end_of_turn(self, done=None, winner=None, history=None):
         """Behind a step: for the envs of `done` (default: the env's own done buffer) -- `history` uint8 [N, 2], if given, receives the members that
@@ -207,3 +225,22 @@ class QPopulation(object):
         self.member.copy_(torch.as_tensor(np.asarray(st["member"], np.uint8)))
         self.counts.copy_(torch.as_tensor(np.asarray(st["counts"], np.int64)))
         self._ctl.copy_(torch.as_tensor(np.asarray(st["ctl"], np.int64)))
+
+
+class SmartQPopulation(QPopulation):
+    """Self-royale for the Smart_State agents (agents/Smart_State/training_scripts/dqn_smart_state_self_royale.py; include/evg.h,
+    evg_smart_population): QPopulation's surface with members that are whatever SmartQNet accepts (59 -> h1 -> h2 -> 5, one (h1, h2) and one final_relu
+    for all) and a head of 5 -- pop(shared, swarm) -> [N, 2, 12, 5] (what step_q takes), pop.seat(...) -> [R, 12, 5], pop.expanded(x, member, seat) ->
+    [..., 5].  Every Q row equals, bit for bit, what SmartQNet writes for it with that member's weights.  The assignment is QPopulation's own -- the same
+    kernels, the same draws: two populations with equal team sizes on one env hold the same members."""
+    OUT = SmartQNet.OUT
+    _NET, _DESC, _FN, _PARAMS, _SIZE_NAME = SmartQNet, _lib.EvgSmartPopulation, "evg_smart_population", ("w1", "b1", "w2", "b2", "w3", "b3"), "(h1, h2)"
+
+    @staticmethod
+    def _size(net):
+        return (net.h1, net.h2)
+
+    def _set_size(self, size, desc=None):
+        self.h1, self.h2 = size
+        if desc is not None:
+            desc.h1, desc.h2 = size

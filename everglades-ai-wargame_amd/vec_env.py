@@ -598,6 +598,13 @@ class EvergladesVecEnv(object):
         from .population import QPopulation
         return QPopulation(self, team0, team1, final_relu=final_relu, max_rows=max_rows)
 
+    def smart_q_population(self, team0, team1=None, final_relu=None, max_rows=None):
+        """Smart_State self-royale (everglades_amd.SmartQPopulation; evg_smart_population): two teams of Smart_State Q networks (whatever smart_qnet()
+        accepts, one (h1, h2) and one final_relu), a member per env and seat drawn each episode -- `pop(shared, swarm)` -> the q [N, 2, 12, 5] step_q()
+        takes, `pop.end_of_turn()` behind the step, `pop.expanded(x, member, seat)` for the target networks.  team1=None plays team0 on both seats."""
+        from .population import SmartQPopulation
+        return SmartQPopulation(self, team0, team1, final_relu=final_relu, max_rows=max_rows)
+
     def smart_replay(self, capacity_turns, n_step=1, gamma=0.999, shaping="normalized_score", seats=0, episode_base=0):
         """The Smart_State learner's n-step replay memory on the device for this env (everglades_amd.SmartReplay: Multi_Step.NStepModule +
         DQNAgent.remember_game_state / end_of_episode / optimize_model's batch).  Storage is allocated once; record / sample / gather run without a host

@@ -47,7 +47,9 @@ extern "C" {
  *    Minimized self-play (a network on each seat): evg_step_minimized_q, evg_step_league_minimized_q (a league whose member q_member is the caller's
  *    second network) -- added, no layout changed;
  *    self-royale (a per-env Minimized network drawn from a population each episode): evg_population_clear / evg_population_assign /
- *    evg_population_qnet with their descriptor evg_population -- added, no layout changed */
+ *    evg_population_qnet with their descriptor evg_population -- added, no layout changed;
+ *    Smart_State self-royale (the same with the 59-h1-h2-5 network): evg_smart_population_clear / evg_smart_population_assign /
+ *    evg_smart_population_qnet with their descriptor evg_smart_population -- added, no layout changed */
 /* 6: evg_smart_get_action (DQNAgent.get_action with epsilon > 0), evg_step_vs_policy_smart (the learner-seat turn that also writes the Smart_State
  *    features), evg_get_run_state / evg_set_run_state (agent objects, returns, win counters: checkpoint / resume); reward / score buffers need 8-byte
  *    alignment only (5 asked 16 of every buffer)
@@ -859,6 +861,53 @@ EVG_API int evg_population_assign(evg_handle* h, const evg_population* pop, cons
  * the descriptor, a NULL member, seat outside 0..1, rows outside 1..2^24 or above scratch_rows. */
 EVG_API int evg_population_qnet(evg_handle* h, const evg_population* pop, int layout, int64_t rows, int seat, const uint8_t* member, const float* in0,
                                 const float* in1, float* q_out, void* stream);
+
+/* ---- Smart_State self-royale: a per-env Smart_State Q network drawn from a population each episode ------------------------------------------------------
+ * agents/Smart_State/training_scripts/dqn_smart_state_self_royale.py (:28, :51-70, :106-107, :148-201): evg_population's twin for the 59-h1-h2-5 network of
+ * evg_smart_qnet.  Member m of team p is the weight set {w1, b1, w2, b2, w3, b3}[p][m] in evg_qnet's layouts (read in place on every call); all members
+ * share h1, h2 and final_relu.  member, counts, ctl, index, first, count, hist and scratch_rows are evg_population's, with the same shapes and meaning.
+ * ASSIGNMENT.  evg_smart_population_clear / _assign run the kernels of evg_population_clear / _assign: the same RNG domain 6, the same draw rule
+ * member = (w * K[p]) >> 32 on the same Philox block.  The draw depends on the handle (seed, env id, episode, seat) and on K[p] alone, not on the
+ * descriptor: on the same handle state they write the same member, counts and history as evg_population_* with the same team sizes, bit for bit -- TWO
+ * POPULATIONS ON ONE HANDLE DRAW THE SAME MEMBERS (with equal team sizes; a Minimized and a Smart_State population, or two of one kind).  Keyed-Philox
+ * handles only.
+ * FORWARD.  evg_smart_population_qnet is evg_smart_qnet with the weight set chosen per row: every Q row equals, bit for bit, what evg_smart_qnet writes
+ * for that row with the weights of team[seat][member[row]].  The bucket pass is evg_population_qnet's (rows of 5 or 60 floats); a row with an id >= K
+ * gets zeros and sets EVG_POP_S_BAD_MEMBER, and such an id never selects weights. */
+typedef struct evg_smart_population {
+    uint32_t struct_size;                       /* sizeof(evg_smart_population)                    */
+    int32_t h1, h2;                             /* hidden sizes of every member, 1..64             */
+    int32_t final_relu;                         /* 0 / 1: the ReLU (NaN kept) on the output layer  */
+    int32_t num_members[2];                     /* K[p], 1..16                                     */
+    const float* w1[2][EVG_POP_MAX_MEMBERS];    /* entries >= K[p] are ignored                     */
+    const float* b1[2][EVG_POP_MAX_MEMBERS];
+    const float* w2[2][EVG_POP_MAX_MEMBERS];
+    const float* b2[2][EVG_POP_MAX_MEMBERS];
+    const float* w3[2][EVG_POP_MAX_MEMBERS];
+    const float* b3[2][EVG_POP_MAX_MEMBERS];
+    uint8_t* member;
+    unsigned long long* counts;
+    unsigned long long* ctl;
+    int32_t* index;
+    int32_t* first;
+    int32_t* count;
+    int32_t* hist;
+    int64_t scratch_rows;
+} evg_smart_population;
+/* As evg_population_clear. */
+EVG_API int evg_smart_population_clear(evg_handle* h, const evg_smart_population* pop, void* stream);
+/* As evg_population_assign: history_out, the tally of winner, the draw, for the envs of mask. */
+EVG_API int evg_smart_population_assign(evg_handle* h, const evg_smart_population* pop, const uint8_t* mask, const int8_t* winner, uint8_t* history_out,
+                                        void* stream);
+/* The forward of `rows` rows (1..2^24, <= scratch_rows), layouts and tensors as evg_smart_qnet, member as in evg_population_qnet:
+ *   EVG_QNET_COMPACT_SEATS  member uint8 [rows][2]; seat ignored; row [r][p] through team p          -> q_out [rows][2][12][5]
+ *   EVG_QNET_COMPACT        member uint8 [rows]; every row through team `seat`                       -> q_out [rows][12][5]
+ *   EVG_QNET_EXPANDED       member uint8 [rows]; every row through team `seat`                       -> q_out [rows][5]
+ * Four launches on `stream` (three of the bucket pass, one forward sized for the worst case), no synchronisation, nothing allocated.  Refused with
+ * EVG_ERR_INVALID (nothing launched): what evg_smart_qnet and evg_population_qnet refuse; struct_size, h1 / h2 outside 1..64, num_members outside 1..16; a
+ * NULL or misaligned weight or scratch pointer; seat outside 0..1; rows outside 1..2^24 or above scratch_rows. */
+EVG_API int evg_smart_population_qnet(evg_handle* h, const evg_smart_population* pop, int layout, int64_t rows, int seat, const uint8_t* member,
+                                      const float* in0, const float* in1, float* q_out, void* stream);
 
 #ifdef __cplusplus
 }
