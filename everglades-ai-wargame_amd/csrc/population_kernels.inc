@@ -10,7 +10,9 @@
 //                                   hist becomes each block's first position in the list, first / count the bins' extents
 //   evg_population_scatter_kernel   bucket pass 3: row -> index[its block's position + counts of the waves before + rank inside the wave (mbcnt)].  No
 //                                   global atomics anywhere, so the list is the stable order: rows ascending inside a member.  Rows whose id is >= K (bin
-//                                   16) get zeros in q_out and set EVG_POP_S_BAD_MEMBER; they are in no member's list
+//                                   16) get zeros in q_out and set EVG_POP_S_BAD_MEMBER; they are in no member's list.  The layout follows the CALL
+//                                   (include/evg.h): seat slot s's list begins at index + s * rows and hist is [S][17][nb], with that call's rows and
+//                                   nb = ceil(rows / 256); the descriptor's scratch_rows bounds both and is no stride
 //   evg_mini_qnet_pop_kernel<EXPANDED>   evg_mini_qnet_kernel with a workgroup belonging to one (seat slot, member): it stages that member's weights once
 //                                   and runs the shared body over the member's list, reading rows through it and writing Q to their original positions
 //   evg_qnet_pop_kernel<EXPANDED>   the same for the Smart_State network (evg_smart_population): evg_qnet_kernel's body (qnet_body.inc) over a member's

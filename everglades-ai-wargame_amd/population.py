@@ -13,6 +13,10 @@ plays env e's current episode, redrawn when the episode ends.
 
 Every Q row equals, bit for bit, what MinimizedQNet writes for it with that member's weights.  The parameters are read in place on every call.  No
 call synchronises with the host, and none allocates when `out` is given (expanded() keeps one id buffer per batch size).
+
+The bucket pass's results stay readable after a forward of `rows` rows: `_bins[0 / 1, s]` are first / count of seat slot s's 17 bins, and slot s's stable
+list begins at word `s * rows` of `_index`, with the rows of that call -- the layout follows the call (include/evg.h); `_index` is allocated as
+[2, scratch_rows] only to bound it, and `_hist` is scratch.
 """
 import ctypes as C
 

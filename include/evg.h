@@ -813,14 +813,18 @@ EVG_API int evg_minimized_qnet(evg_handle* h, const evg_mini_qnet* net, int layo
  *   member   uint8 [N][2]          the member of team p that plays env e in its current episode
  *   counts   uint64 [2][16][4]     {games, wins, ties, losses} of member m of team p, seen from seat p
  *   ctl      uint64 [2]            {status bits EVG_POP_S_* (sticky until evg_population_clear), reserved}
- *   index    int32 [2][scratch_rows], first / count int32 [2][17], hist int32 [2][17][ceil(scratch_rows / 256)]: the bucket pass's scratch and results
- *                                  (below); scratch_rows >= the rows of every evg_population_qnet call
+ *   index    int32, 2 * scratch_rows words; first / count int32 [2][17]; hist int32, 2 * 17 * ceil(scratch_rows / 256) words: the bucket pass's results
+ *                                  and scratch (below); scratch_rows >= the rows of every evg_population_qnet call.  scratch_rows BOUNDS index and
+ *                                  hist, it is not their stride: a call of `rows` rows lays index out as [S][rows] (S seat slots: 2 for
+ *                                  EVG_QNET_COMPACT_SEATS, else 1) -- seat slot s's list begins at index + s * rows, with the rows of THAT call -- and
+ *                                  leaves the words behind S * rows as they were; hist is scratch, [S][17][ceil(rows / 256)] during the call
  * ASSIGNMENT.  The member of (env e, seat p) for episode k is random.choice(team) restated on a keyed draw (domain 6):
  * member = (w * K[p]) >> 32 with w = word .x of the Philox block (domain 6, block 0, turn 0, node 0, player p, group 0, episode k, global env id).  A team
  * of one draws nothing observable: its member is 0.  Keyed-Philox handles only.
  * FORWARD.  evg_population_qnet is evg_minimized_qnet with the weight set chosen per row; every Q row equals, bit for bit, what evg_minimized_qnet
  * writes for that row with the weights of team[seat][member[row]].  It first buckets the rows by member id -- a stable counting sort without global
- * atomics: index[s][first[s][m] .. + count[s][m]) lists the rows of member m in ascending order, bin 16 the rows whose id is >= K -- and then runs one
+ * atomics: with index read as [S][rows] of this call, index[s][first[s][m] .. + count[s][m]) lists the rows of member m of seat slot s in ascending order,
+ * bin 16 the rows whose id is >= K; first / count [s] are the 17 bins' extents, valid until the next call -- and then runs one
  * workgroup set per (seat, member) over its list.  A row with an id >= K gets zeros and sets EVG_POP_S_BAD_MEMBER; such an id never selects weights. */
 #define EVG_POP_MAX_MEMBERS 16
 #define EVG_POP_MAX_ROWS (1 << 24)
