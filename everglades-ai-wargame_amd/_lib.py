@@ -11,6 +11,9 @@ LIB_PATH = os.path.join(HERE, "libevg.so")                # the product library;
 DIAG_LIB_PATH = os.path.join(HERE, "libevg_diag.so")      # `make -C csrc diag`: phase ablation, 16-envs-per-wave variant, forced IEEE division
 # `make -C csrc graphs`: rollout launch plans replayed as library-owned hipGraphs (A/B build; measured slower)
 GRAPHS_LIB_PATH = os.path.join(HERE, "libevg_graphs.so")
+# `make -C csrc priority`: the product plus the three entry points of include/evg_replay_priority.h (PrioritizedSmartReplay loads it: load_priority)
+PRIORITY_LIB_PATH = os.path.join(HERE, "libevg_priority.so")
+PRIORITY_EXPORTS = ["evg_replay_priority_clear", "evg_replay_update_priorities", "evg_replay_sample_prioritized"]
 STAMPS_LIB_PATH = os.path.join(HERE, "libevg_stamps.so")  # `make -C csrc stamps`: in-kernel phase stamps (tools/stamps.py)
 
 NUM_PLAYERS, NUM_GROUPS, NUM_NODES, NUM_UNITS, NUM_ACTIONS, OBS_LEN = 2, 12, 11, 100, 7, 105
@@ -107,6 +110,11 @@ class EvgReplay(C.Structure):
     ]
 
 
+class EvgReplayPriority(C.Structure):
+    """evg_replay_priority of include/evg.h: the weight plane and work space of prioritized sampling (device pointers the caller owns)."""
+    _fields_ = [("alpha", C.c_float), ("plane", C.c_void_p), ("pscan", C.c_void_p), ("pctl", C.c_void_p)]
+
+
 class EvgQnet(C.Structure):
     """evg_qnet of include/evg.h: the Smart_State Q network's weights (device pointers the caller owns, nn.Linear layout), one or two sets."""
     _fields_ = [
@@ -165,7 +173,7 @@ MINI_QNET_MAX_HIDDEN, MINI_QNET_OUT = 128, 11                  # EVG_MINI_QNET_M
 
 SHAPE_NAMES = ["normalized_score", "basic_reward", "penalize_long_games", "reward_short_games", "transition", "custom"]   # index = EVG_SHAPE_*
 REPLAY_F_NOT_DONE, REPLAY_F_FINAL = 1, 2
-REPLAY_S_EMPTY, REPLAY_S_BAD_HANDLE = 1, 2
+REPLAY_S_EMPTY, REPLAY_S_BAD_HANDLE, REPLAY_S_BAD_PRIORITY = 1, 2, 4
 
 
 class EvgError(RuntimeError):
@@ -246,6 +254,11 @@ def load(path=None):
     L.evg_replay_size.argtypes = [vp, rp, vp]
     L.evg_replay_sample.argtypes = [vp, rp, C.c_int, C.c_uint64, vp, vp, vp, vp, vp, vp, vp]
     L.evg_replay_gather.argtypes = [vp, rp, C.c_int, vp, vp, vp, vp, vp, vp, vp]
+    if hasattr(L, "evg_replay_priority_clear"):      # libevg_priority.so only
+        pr = C.POINTER(EvgReplayPriority)
+        L.evg_replay_priority_clear.argtypes = [vp, rp, pr, vp]
+        L.evg_replay_update_priorities.argtypes = [vp, rp, pr, C.c_int, vp, vp, vp]
+        L.evg_replay_sample_prioritized.argtypes = [vp, rp, C.c_int, C.c_uint64, vp, vp, vp, vp, vp, vp, pr, C.c_float, vp, vp]
     L.evg_smart_qnet.argtypes = [vp, C.POINTER(EvgQnet), C.c_int, C.c_int64, vp, vp, vp, vp]
     lp = C.POINTER(EvgLeague)
     L.evg_league_clear.argtypes = [vp, lp, vp]
@@ -303,6 +316,16 @@ def load(path=None):
     if hasattr(L, "evg_diag_configure"):      # diagnostic libraries only
         L.evg_diag_configure.argtypes = [vp, C.c_uint32, C.c_int, C.c_int]
     _libs[path] = L
+    return L
+
+
+def load_priority():
+    """Load libevg_priority.so: libevg.so's sources built with -DEVG_PRIORITY, which exports the entry points of include/evg.h plus PRIORITY_EXPORTS
+    (include/evg_replay_priority.h).  A handle of libevg.so is valid in it; a failed call's text is its own evg_last_error (check(rc, this library))."""
+    L = load(PRIORITY_LIB_PATH)
+    missing = [n for n in PRIORITY_EXPORTS if not hasattr(L, n)]
+    if missing:
+        raise EvgError("%s does not export %s; rebuild it (make -C everglades-ai-wargame_amd/csrc priority)" % (PRIORITY_LIB_PATH, ", ".join(missing)))
     return L
 
 

@@ -955,6 +955,51 @@ int evg_replay_gather(evg_handle* h, const evg_replay* m, int batch, const int32
     return launched("replay gather", launch_replay_gather(h->S, *m, batch, handles, swarm_obs, action, next_state, reward, not_done, stream));
 } catch (...) { return on_exception(); }
 
+// ---- prioritized sampling over the replay memory (include/evg_replay_priority.h; libevg_priority.so only) ----
+#ifdef EVG_PRIORITY
+static int check_priority(const evg_replay_priority* p) {
+    if (!p) return fail(EVG_ERR_INVALID, "null priority descriptor");
+    if (!(p->alpha >= 0.0f && p->alpha <= 1.0f)) return fail(EVG_ERR_INVALID, "replay priority: alpha must lie in [0, 1] (got %g)", (double)p->alpha);
+    if (!p->plane || !p->pscan || !p->pctl) return fail(EVG_ERR_INVALID, "replay priority: plane, pscan and pctl are required");
+    EVG_NEED_ALIGNED16(p->plane); EVG_NEED_ALIGNED8(p->pscan); EVG_NEED_ALIGNED8(p->pctl);
+    return EVG_OK;
+}
+
+int evg_replay_priority_clear(evg_handle* h, const evg_replay* m, const evg_replay_priority* p, void* stream) try {
+    { const int rc = check_replay(h, m); if (rc) return rc; }
+    { const int rc = check_priority(p); if (rc) return rc; }
+    EVG_ON_DEVICE(h);
+    return launched("replay priority clear", launch_replay_priority_clear(h->S, *m, *p, stream));
+} catch (...) { return on_exception(); }
+
+int evg_replay_update_priorities(evg_handle* h, const evg_replay* m, const evg_replay_priority* p, int batch, const int32_t* handles,
+                                 const float* priorities, void* stream) try {
+    { const int rc = check_replay(h, m); if (rc) return rc; }
+    { const int rc = check_priority(p); if (rc) return rc; }
+    if (batch < 1) return fail(EVG_ERR_INVALID, "replay: batch must be >= 1 (got %d)", batch);
+    if (batch > (1 << 24)) return fail(EVG_ERR_INVALID, "replay: batch %d > 2^24", batch);
+    if (!handles || !priorities) return fail(EVG_ERR_INVALID, "replay: handles and priorities are required");
+    EVG_NEED_ALIGNED16(handles);
+    EVG_ON_DEVICE(h);
+    return launched("replay priority update", launch_replay_priority_update(h->S, *m, *p, batch, handles, priorities, stream));
+} catch (...) { return on_exception(); }
+
+int evg_replay_sample_prioritized(evg_handle* h, const evg_replay* m, int batch, uint64_t seed, float* swarm_obs, int64_t* action, float* next_state,
+                                  float* reward, uint8_t* not_done, int32_t* handles, const evg_replay_priority* p, float beta, float* weights_out,
+                                  void* stream) try {
+    { const int rc = check_replay(h, m); if (rc) return rc; }
+    { const int rc = check_priority(p); if (rc) return rc; }
+    { const int rc = check_batch_out(batch, swarm_obs, action, next_state, reward, not_done, handles); if (rc) return rc; }
+    if (!(beta >= 0.0f) || beta > 3.402823466e+38f) return fail(EVG_ERR_INVALID, "replay priority: beta must be finite and >= 0 (got %g)", (double)beta);
+    if (!weights_out) return fail(EVG_ERR_INVALID, "replay: weights_out is required");
+    EVG_NEED_ALIGNED16(weights_out);
+    EVG_ON_DEVICE(h);
+    int rc = launch_replay_priority_draw(h->S, *m, *p, batch, seed, beta, handles, weights_out, stream);
+    if (!rc) rc = launch_replay_gather(h->S, *m, batch, handles, swarm_obs, action, next_state, reward, not_done, stream);
+    return launched("replay sample prioritized", rc);
+} catch (...) { return on_exception(); }
+#endif
+
 // ---- the Smart_State Q network (include/evg.h, evg_smart_qnet) ----
 int evg_smart_qnet(evg_handle* h, const evg_qnet* net, int layout, int64_t rows, const float* in0, const float* in1, float* q_out, void* stream) try {
     if (!h || !net) return fail(EVG_ERR_INVALID, "null handle or network descriptor");

@@ -23,6 +23,9 @@
 #pragma once
 #include <stdint.h>
 #include "../../include/evg.h"
+#ifdef EVG_PRIORITY
+#include "../../include/evg_replay_priority.h"
+#endif
 #include "evg_rng.h"
 
 namespace evg {
@@ -238,6 +241,14 @@ int launch_replay_count(const DevState& S, const evg_replay& m, int count_call /
 int launch_replay_draw(const DevState& S, const evg_replay& m, int batch, uint64_t seed, int32_t* handles, void* stream);
 int launch_replay_gather(const DevState& S, const evg_replay& m, int batch, const int32_t* handles, float* swarm_obs, int64_t* action, float* next_state,
                          float* reward, uint8_t* not_done, void* stream);
+#ifdef EVG_PRIORITY
+// prioritized sampling over that memory (replay_priority_kernels.inc, libevg_priority.so); `m`, `p` and beta are validated by the caller (evg_abi.hip)
+int launch_replay_priority_clear(const DevState& S, const evg_replay& m, const evg_replay_priority& p, void* stream);
+int launch_replay_priority_update(const DevState& S, const evg_replay& m, const evg_replay_priority& p, int batch, const int32_t* handles,
+                                  const float* priorities, void* stream);
+int launch_replay_priority_draw(const DevState& S, const evg_replay& m, const evg_replay_priority& p, int batch, uint64_t seed, float beta, int32_t* handles,
+                                float* weights /* out: the importance weights */, void* stream);
+#endif
 // the Smart_State Q network's forward pass (qnet_kernels.inc); `net` and the sizes are validated by the caller (evg_abi.hip)
 int launch_smart_qnet(const evg_qnet& net, int layout, long long rows, const float* in0, const float* in1, float* q_out, int num_cu, void* stream);
 // the Minimized agents' decode and Q network (minimized_decode.inc, minimized_qnet.inc); arguments validated by the caller (evg_abi.hip)

@@ -76,6 +76,9 @@ namespace evg {
 
 #include "side_kernels.inc"     // pack, chunk-queue check, reset, seeding, action generators, fog planes, Smart_State features
 #include "replay_kernels.inc"   // the Smart_State learner's n-step replay memory: record, count, draw, gather
+#ifdef EVG_PRIORITY              // `make priority` (libevg_priority.so): the product's kernels plus ...
+#include "replay_priority_kernels.inc"   // prioritized sampling over that memory: the weight plane's update pair, the q scan, draw and importance weights
+#endif
 #include "qnet_kernels.inc"     // the Smart_State Q network's forward pass (inference) on v_mfma_f32_16x16x4_f32
 #include "league_kernels.inc"   // the opponent league: clear, assign after an explicit reset, importance weights
 #include "minimized_qnet.inc"   // the Minimized agents' Q network's forward pass (59 -> h1 <= 128 -> 11) on v_mfma_f32_16x16x4_f32

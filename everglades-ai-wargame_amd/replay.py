@@ -184,7 +184,7 @@ class SmartReplay(object):
         return self.ctl[0]
 
     def status(self):
-        """The memory's sticky status bits (REPLAY_S_EMPTY, REPLAY_S_BAD_HANDLE); synchronises."""
+        """The memory's sticky status bits (REPLAY_S_EMPTY, REPLAY_S_BAD_HANDLE, REPLAY_S_BAD_PRIORITY); synchronises."""
         return int(self.ctl[1].item())
 
     def check(self):
@@ -194,3 +194,106 @@ class SmartReplay(object):
             what = [w for bit, w in ((_lib.REPLAY_S_EMPTY, "a sample from an empty memory"), (_lib.REPLAY_S_BAD_HANDLE, "a gather of a handle that names "
                                                                                                                          "no transition")) if st & bit]
             raise _lib.EvgError("replay memory status %d: %s" % (st, ", ".join(what)))
+
+
+class PrioritizedSmartReplay(SmartReplay):
+    """SmartReplay that also samples by priority (agents/DQN/PrioritizedMemory.py: sample / update_priorities; include/evg_replay_priority.h, whose three
+    entry points libevg_priority.so exports beside those of libevg.so: it is loaded here and takes the env's handle).
+
+        mem = env.prioritized_replay(capacity_turns=8, alpha=0.6, n_step=1, shaping="reward_short_games")
+        swarm_obs, action, next_state_swarms, reward, not_done, weights, handles = mem.sample(1024, seed=t, beta=0.4)
+        mem.update_priorities(handles, td.abs() + 1e-5)
+
+    The library stores the priorities handed back and draws by them; the TD error and the weighted loss are the consumer's.  Three documented differences
+    from the reference class, next to the two of SmartReplay: (1) a transition that was never updated weighs wmax, the largest weight ever stored since
+    the last clear(), AS OF THE DRAW (the reference fixes priorities.max() over the current values at push time); (2) when one update names a transition
+    several times the LARGEST priority is kept (the reference's loop keeps the last); (3) probabilities are q / Q with integer weights quantised to 2^-32
+    of the maximum and floored at one unit, so that a host model reproduces every draw bit for bit and nothing is undrawable."""
+
+    def __init__(self, env, capacity_turns, alpha=0.6, **kw):
+        torch = _torch()
+        alpha = float(alpha)
+        if not 0.0 <= alpha <= 1.0:                                                     # (NaN fails both comparisons)
+            raise ValueError("alpha must lie in [0, 1] (got %r)" % (alpha,))
+        self.alpha = alpha
+        self._p = None
+        self.P = _lib.load_priority()                                                   # libevg_priority.so: the three entry points used below
+        SmartReplay.__init__(self, env, capacity_turns, **kw)
+        dev, R = env.device, self.slots * self.N * self.S
+        with torch.cuda.device(dev):
+            self._plane = torch.zeros((self.slots, self.N, self.S, 8), dtype=torch.float32, device=dev)
+            self._pscan = torch.zeros(((R + 3) // 4 + 2 * ((R + 1023) // 1024),), dtype=torch.int64, device=dev)      # EVG_REPLAY_PSCAN_WORDS
+            self.pctl = torch.zeros((4,), dtype=torch.int64, device=dev)
+        p = _lib.EvgReplayPriority()
+        p.alpha, p.plane, p.pscan, p.pctl = alpha, self._plane.data_ptr(), self._pscan.data_ptr(), self.pctl.data_ptr()
+        self._p = p
+        self._wout = {}
+        self.clear()
+
+    def _pcheck(self, rc):
+        if rc:
+            _lib.check(rc, self.P)
+
+    @property
+    def priorities(self):
+        """float32 [slots, N, S, 8] view of the plane: entries 0..6 the weights priority ** alpha of a record's transitions (0 = never updated), entry 7
+        the record's stamp as int bits."""
+        return self._plane
+
+    @property
+    def wmax(self):
+        """float32 0-d device tensor: the largest weight stored since the last clear() (what a never-updated transition weighs)."""
+        return self.pctl[:1].view(_torch().float32)[0]
+
+    def clear(self):
+        """SmartReplay.clear(), and the plane back to "never updated" with wmax = 1."""
+        SmartReplay.clear(self)
+        if self._p is not None:
+            self._pcheck(self.P.evg_replay_priority_clear(self.env._h, C.byref(self._d), C.byref(self._p), self.env._stream()))
+
+    def sample(self, batch_size, seed, beta=0.4):
+        """SmartReplay.sample's five tensors for transitions drawn by weight, with replacement, then weights float32 [B] -- (T q / Q) ** -beta over the
+        batch's largest -- and the drawn handles int32 [B, 4] to hand back to update_priorities.  Shares the call counter `sample_calls` with uniform
+        samples (`uniform_sample`)."""
+        B = int(batch_size)
+        if B < 1:
+            raise ValueError("batch_size must be >= 1")
+        beta = float(beta)
+        if not 0.0 <= beta < float("inf"):
+            raise ValueError("beta must be finite and >= 0 (got %r)" % (beta,))
+        o = self._outputs(B)
+        w = self._wout.get(B)
+        if w is None:
+            torch = _torch()
+            with torch.cuda.device(self.env.device):
+                w = self._wout[B] = torch.empty((B,), dtype=torch.float32, device=self.env.device)
+        p = [C.c_void_p(t.data_ptr()) for t in o]
+        rc = self.P.evg_replay_sample_prioritized(self.env._h, C.byref(self._d), B, int(seed) & 0xFFFFFFFFFFFFFFFF, p[0], p[1], p[2], p[3], p[4], p[5],
+                                                  C.byref(self._p), beta, C.c_void_p(w.data_ptr()), self.env._stream())
+        self._pcheck(rc)
+        return o[:5] + (w, o[5])
+
+    def uniform_sample(self, batch_size, seed, return_handles=False):
+        """SmartReplay.sample: the uniform draw over the same memory."""
+        return SmartReplay.sample(self, batch_size, seed, return_handles)
+
+    def update_priorities(self, handles, priorities):
+        """handles int32 [B, 4] as sample() returned them, priorities float32 [B] (> 0 and finite; e.g. |td| + 1e-5).  A bad priority or handle is
+        skipped and sets REPLAY_S_BAD_PRIORITY / REPLAY_S_BAD_HANDLE in status()."""
+        torch = _torch()
+        if not isinstance(handles, torch.Tensor) or handles.dim() != 2 or handles.shape[1] != 4 or handles.shape[0] < 1:
+            raise ValueError("handles must be an int32 tensor [B, 4] with B >= 1")
+        B = int(handles.shape[0])
+        self.env._user(handles, (B, 4), torch.int32, "handles")
+        self.env._user(priorities, (B,), torch.float32, "priorities")
+        if handles.data_ptr() % 16:
+            raise ValueError("handles must be 16-byte aligned")
+        rc = self.P.evg_replay_update_priorities(self.env._h, C.byref(self._d), C.byref(self._p), B, C.c_void_p(handles.data_ptr()),
+                                                 C.c_void_p(priorities.data_ptr()), self.env._stream())
+        self._pcheck(rc)
+
+    def check(self):
+        """SmartReplay.check(), and a priority update that met a bad priority."""
+        if self.status() & _lib.REPLAY_S_BAD_PRIORITY:
+            raise _lib.EvgError("replay memory status %d: a priority update got a priority that is NaN, infinite or <= 0" % self.status())
+        SmartReplay.check(self)

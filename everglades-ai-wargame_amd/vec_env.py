@@ -612,6 +612,14 @@ class EvergladesVecEnv(object):
         from .replay import SmartReplay
         return SmartReplay(self, capacity_turns, n_step=n_step, gamma=gamma, shaping=shaping, seats=seats, episode_base=episode_base)
 
+    def prioritized_replay(self, capacity_turns, alpha=0.6, n_step=1, gamma=0.999, shaping="normalized_score", seats=0, episode_base=0):
+        """smart_replay() that also samples by priority (everglades_amd.PrioritizedSmartReplay: agents/DQN/PrioritizedMemory.py's sample and
+        update_priorities over the same ring): sample(batch, seed, beta) draws by priority ** alpha and returns importance weights and handles,
+        update_priorities(handles, priorities) hands the new priorities back.  No host synchronisation."""
+        from .replay import PrioritizedSmartReplay
+        return PrioritizedSmartReplay(self, capacity_turns, alpha=alpha, n_step=n_step, gamma=gamma, shaping=shaping, seats=seats,
+                                      episode_base=episode_base)
+
     def smart_qnet(self, net, final_relu=None):
         """The Smart_State Q network's forward pass on this env's device, one launch per call (everglades_amd.SmartQNet, evg_smart_qnet): `net` is the
         reference's QNetwork (final ReLU), an nn.Sequential Linear/ReLU/Linear/ReLU/Linear[/ReLU], a 6-tuple (w1, b1, w2, b2, w3, b3) with final_relu,

@@ -14,7 +14,10 @@ With device_net=True the acting forward (policy on the compact features) and the
 one launch each (env.smart_qnet, evg_smart_qnet: the modules' parameters read in place, so Adam's steps and load_state_dict are seen); the policy
 forward inside optimize_model stays torch (its gradient is the loss's).
 
-    python examples/smart_state_training.py [envs] [turns] [batch] [device_net]
+With --prioritized the memory is env.prioritized_replay (agents/DQN/PrioritizedMemory.py: alpha 0.6, beta 0.4): the batch is drawn by priority, the
+Huber loss is weighted per sample by the importance weights and |td| + 1e-5 goes back as the new priorities (evg_replay_update_priorities).
+
+    python examples/smart_state_training.py [envs] [turns] [batch] [device_net] [--prioritized]
 """
 import os
 import sys
@@ -38,8 +41,10 @@ def q_values(net, shared, swarm):
     return net(evg.EvergladesVecEnv.expand_smart_state(shared, swarm)).contiguous()
 
 
-def optimize_model(policy, target, opt, batch, target_eval=None):
-    """DQNAgent.optimize_model (DQNAgent.py:336-385) on the sampled operands.  target_eval: the target network on the device (SmartQNet.expanded)."""
+def optimize_model(policy, target, opt, batch, target_eval=None, weights=None):
+    """DQNAgent.optimize_model (DQNAgent.py:336-385) on the sampled operands.  target_eval: the target network on the device (SmartQNet.expanded).
+    weights: importance weights [B] of a prioritized batch -- the loss is then the weighted mean of the per-sample Huber terms and the call returns
+    (loss, new priorities |td| + 1e-5)."""
     swarm_obs, action, next_state, reward, not_done = batch
     predicted = policy(swarm_obs).gather(1, action.unsqueeze(1))
     with torch.no_grad():
@@ -47,16 +52,21 @@ def optimize_model(policy, target, opt, batch, target_eval=None):
         nxt = torch.where(not_done[:, None, None], nxt, torch.zeros_like(nxt))
         future = nxt.amax(2).mean(1)
         estimated = future * (GAMMA ** N_STEP) + reward
-    loss = F.smooth_l1_loss(predicted, estimated.unsqueeze(1))
+    if weights is None:
+        loss = F.smooth_l1_loss(predicted, estimated.unsqueeze(1))
+    else:
+        loss = (F.smooth_l1_loss(predicted, estimated.unsqueeze(1), reduction="none").squeeze(1) * weights).mean()
     opt.zero_grad()
     loss.backward()
     for p in policy.parameters():
         p.grad.data.clamp_(-1, 1)
     opt.step()
+    if weights is not None:
+        return loss.detach(), ((predicted.detach().squeeze(1) - estimated).abs() + 1e-5).contiguous()
     return loss.detach()
 
 
-def main(num_envs=8192, turns=300, batch=1024, opponent="swarm_agent", seat=0, seed=1, epsilon=0.3, device_net=False):
+def main(num_envs=8192, turns=300, batch=1024, opponent="swarm_agent", seat=0, seed=1, epsilon=0.3, device_net=False, prioritized=False):
     env = evg.EvergladesVecEnv(num_envs, seed=seed, auto_reset=True)
     dev = env.device
     policy, target = make_qnet(dev, 0), make_qnet(dev, 0)
@@ -65,7 +75,10 @@ def main(num_envs=8192, turns=300, batch=1024, opponent="swarm_agent", seat=0, s
     act_net = target_eval = None
     if device_net:
         act_net, target_eval = env.smart_qnet(policy), env.smart_qnet(target).expanded
-    mem = env.smart_replay(8, n_step=N_STEP, gamma=GAMMA, shaping="reward_short_games", seats=seat)
+    if prioritized:
+        mem = env.prioritized_replay(8, alpha=0.6, n_step=N_STEP, gamma=GAMMA, shaping="reward_short_games", seats=seat)
+    else:
+        mem = env.smart_replay(8, n_step=N_STEP, gamma=GAMMA, shaping="reward_short_games", seats=seat)
     env.reset()
     env.smart_state_compact(-1, env.observe_seat(seat), *mem.slot_features(0))   # record 0's features
     losses = []
@@ -76,7 +89,12 @@ def main(num_envs=8192, turns=300, batch=1024, opponent="swarm_agent", seat=0, s
             q = q_values(policy, *mem.slot_features(t)) if act_net is None else act_net(*mem.slot_features(t))
         env.step_vs_q(opponent, q, epsilon, seat=seat, features=mem.slot_features(t + 1), directions=mem.slot_directions(t))
         mem.record()
-        if t >= N_STEP + 1:
+        if t >= N_STEP + 1 and prioritized:
+            out = mem.sample(batch, seed=seed, beta=0.4)
+            loss, priorities = optimize_model(policy, target, opt, out[:5], target_eval, weights=out[5])
+            mem.update_priorities(out[6], priorities)
+            losses.append(loss)
+        elif t >= N_STEP + 1:
             losses.append(optimize_model(policy, target, opt, mem.sample(batch, seed=seed), target_eval))
         if t % 100 == 99:
             target.load_state_dict(policy.state_dict())
@@ -92,5 +110,6 @@ def main(num_envs=8192, turns=300, batch=1024, opponent="swarm_agent", seat=0, s
 
 
 if __name__ == "__main__":
-    a = sys.argv[1:]
-    main(int(a[0]) if a else 8192, int(a[1]) if len(a) > 1 else 300, int(a[2]) if len(a) > 2 else 1024, device_net=len(a) > 3 and a[3] in ("1", "device_net"))
+    a = [x for x in sys.argv[1:] if x != "--prioritized"]
+    main(int(a[0]) if a else 8192, int(a[1]) if len(a) > 1 else 300, int(a[2]) if len(a) > 2 else 1024, device_net=len(a) > 3 and a[3] in ("1", "device_net"),
+         prioritized="--prioritized" in sys.argv[1:])

@@ -550,6 +550,17 @@ EVG_API int evg_abi_version(void);
  *   gamma_pow   double [n_step]           gamma ** k for k < n_step, computed on the HOST (Python's float power; a device pow may differ in the last bit)
  *   scan        int32 [EVG_REPLAY_SCAN_INTS(slots, N, S)]  work space of evg_replay_sample / evg_replay_size
  *   ctl         uint64 [4]                {sample calls so far, status bits EVG_REPLAY_S_*, transitions counted by the last scan, call index in use}
+ *
+ * Prioritized sampling (include/evg_replay_priority.h, libevg_priority.so) adds three caller-owned buffers next to these:
+ *   plane       float [slots][N][S][8]    one 32-byte row per record, 16-byte aligned.  Entry k < 7: the weight w = priority ** alpha of the record's
+ *                                         k-th transition (k counts the record's transition rows in ascending order-row order); 0.0f = never updated.
+ *                                         Entry 7, as int bits: the stamp of the record the entries belong to,
+ *                                             0x80000000 | (episode & 0x7FFFFF) << 8 | (turn & 0xFF)       from the record's meta {turn, episode}.
+ *                                         A row whose stamp differs from its record's meta holds a previous occupant's weights: all its transitions
+ *                                         count as never updated.  (So evg_replay_record knows nothing of the plane and recording costs nothing more.)
+ *   pscan       uint64 [EVG_REPLAY_PSCAN_WORDS(slots, N, S)]  work space of the prioritized sample, 8-byte aligned
+ *   pctl        uint64 [4]                {float bits of wmax: the largest weight stored since the last clear (1.0f after it); Q: the sum of the integer
+ *                                         weights of the last scan; the least integer weight of the last batch; 0}, 8-byte aligned
  * ------------------------------------------------------------------------------------------------------------------------------------------------- */
 #define EVG_REPLAY_SHARED_STRIDE(N, S) (((int64_t)(N) * (S) * 34 + 3) / 4 * 4)
 #define EVG_REPLAY_DIRS_STRIDE(N, S) (((int64_t)(N) * (S) * 14 + 3) / 4 * 4)
