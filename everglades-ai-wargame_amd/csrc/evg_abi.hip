@@ -1001,7 +1001,10 @@ int evg_replay_sample_prioritized(evg_handle* h, const evg_replay* m, int batch,
 #endif
 
 // ---- the Smart_State Q network (include/evg.h, evg_smart_qnet) ----
-int evg_smart_qnet(evg_handle* h, const evg_qnet* net, int layout, int64_t rows, const float* in0, const float* in1, float* q_out, void* stream) try {
+// (the checks of evg_smart_qnet and, in libevg_bf16.so, of evg_smart_qnet_bf16: the same refusals, then the entry point's own launch)
+typedef int (*smart_qnet_launch)(const evg_qnet&, int, long long, const float*, const float*, float*, int, void*);
+static int smart_qnet_call(evg_handle* h, const evg_qnet* net, int layout, int64_t rows, const float* in0, const float* in1, float* q_out, void* stream,
+                           smart_qnet_launch launch) {
     if (!h || !net) return fail(EVG_ERR_INVALID, "null handle or network descriptor");
     if (net->struct_size != sizeof(evg_qnet)) return fail(EVG_ERR_INVALID, "qnet: struct_size %u != sizeof(evg_qnet) %zu", net->struct_size, sizeof(evg_qnet));
     if (net->h1 < 1 || net->h1 > EVG_QNET_MAX_HIDDEN || net->h2 < 1 || net->h2 > EVG_QNET_MAX_HIDDEN)
@@ -1023,8 +1026,18 @@ int evg_smart_qnet(evg_handle* h, const evg_qnet* net, int layout, int64_t rows,
     if (!in0 || !q_out || (layout != EVG_QNET_EXPANDED && !in1)) return fail(EVG_ERR_INVALID, "qnet: in0, q_out and (compact layouts) in1 are required");
     EVG_NEED_ALIGNED16(in0); EVG_NEED_ALIGNED16(in1); EVG_NEED_ALIGNED16(q_out);
     EVG_ON_DEVICE(h);
-    return launched("qnet", launch_smart_qnet(*net, layout, (long long)rows, in0, in1, q_out, h->caps.cus, stream));
+    return launched("qnet", launch(*net, layout, (long long)rows, in0, in1, q_out, h->caps.cus, stream));
+}
+
+int evg_smart_qnet(evg_handle* h, const evg_qnet* net, int layout, int64_t rows, const float* in0, const float* in1, float* q_out, void* stream) try {
+    return smart_qnet_call(h, net, layout, rows, in0, in1, q_out, stream, launch_smart_qnet);
 } catch (...) { return on_exception(); }
+
+#ifdef EVG_BF16     // include/evg_qnet_bf16.h; libevg_bf16.so only
+int evg_smart_qnet_bf16(evg_handle* h, const evg_qnet* net, int layout, int64_t rows, const float* in0, const float* in1, float* q_out, void* stream) try {
+    return smart_qnet_call(h, net, layout, rows, in0, in1, q_out, stream, launch_smart_qnet_bf16);
+} catch (...) { return on_exception(); }
+#endif
 
 // ---- the opponent league (include/evg.h, evg_league) ----
 static int check_league(const evg_handle* h, const evg_league* lg) {
@@ -1223,7 +1236,10 @@ int evg_step_league_minimized_q(evg_handle* h, const float* q, float epsilon0, f
     return launched("step", launch_step_minimized2(h->S, io, h->cfg.obs_dtype, h->caps, stream));
 } catch (...) { return on_exception(); }
 
-int evg_minimized_qnet(evg_handle* h, const evg_mini_qnet* net, int layout, int64_t rows, const float* in0, const float* in1, float* q_out, void* stream) try {
+// (the checks of evg_minimized_qnet and, in libevg_bf16.so, of evg_minimized_qnet_bf16: the same refusals, then the entry point's own launch)
+typedef int (*mini_qnet_launch)(const evg_mini_qnet&, int, long long, const float*, const float*, float*, int, void*);
+static int minimized_qnet_call(evg_handle* h, const evg_mini_qnet* net, int layout, int64_t rows, const float* in0, const float* in1, float* q_out,
+                               void* stream, mini_qnet_launch launch) {
     if (!h || !net) return fail(EVG_ERR_INVALID, "null handle or network descriptor");
     if (net->struct_size != sizeof(evg_mini_qnet))
         return fail(EVG_ERR_INVALID, "minimized qnet: struct_size %u != sizeof(evg_mini_qnet) %zu", net->struct_size, sizeof(evg_mini_qnet));
@@ -1247,8 +1263,19 @@ int evg_minimized_qnet(evg_handle* h, const evg_mini_qnet* net, int layout, int6
         return fail(EVG_ERR_INVALID, "minimized qnet: in0, q_out and (compact layouts) in1 are required");
     EVG_NEED_ALIGNED16(in0); EVG_NEED_ALIGNED16(in1); EVG_NEED_ALIGNED16(q_out);
     EVG_ON_DEVICE(h);
-    return launched("minimized qnet", launch_minimized_qnet(*net, layout, (long long)rows, in0, in1, q_out, h->caps.cus, stream));
+    return launched("minimized qnet", launch(*net, layout, (long long)rows, in0, in1, q_out, h->caps.cus, stream));
+}
+
+int evg_minimized_qnet(evg_handle* h, const evg_mini_qnet* net, int layout, int64_t rows, const float* in0, const float* in1, float* q_out, void* stream) try {
+    return minimized_qnet_call(h, net, layout, rows, in0, in1, q_out, stream, launch_minimized_qnet);
 } catch (...) { return on_exception(); }
+
+#ifdef EVG_BF16     // include/evg_qnet_bf16.h; libevg_bf16.so only
+int evg_minimized_qnet_bf16(evg_handle* h, const evg_mini_qnet* net, int layout, int64_t rows, const float* in0, const float* in1, float* q_out,
+                            void* stream) try {
+    return minimized_qnet_call(h, net, layout, rows, in0, in1, q_out, stream, launch_minimized_qnet_bf16);
+} catch (...) { return on_exception(); }
+#endif
 
 // ---- self-royale (include/evg.h: evg_population_clear / _assign / _qnet) ----
 static int check_population(const evg_handle* h, const evg_population* pop, bool forward) {

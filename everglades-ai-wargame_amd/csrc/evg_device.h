@@ -26,6 +26,9 @@
 #ifdef EVG_PRIORITY
 #include "../../include/evg_replay_priority.h"
 #endif
+#ifdef EVG_BF16
+#include "../../include/evg_qnet_bf16.h"
+#endif
 #include "evg_rng.h"
 
 namespace evg {
@@ -257,6 +260,12 @@ int launch_step_minimized2(const DevState& S, const StepIO& io, int obs_dtype, c
 int launch_minimized_actions(const DevState& S, const float* q, int32_t* actions, void* stream, const SmartExplore* explore /* NULL: get_best_actions only */,
                              uint8_t* explored /* device [N] or NULL */);
 int launch_minimized_qnet(const evg_mini_qnet& net, int layout, long long rows, const float* in0, const float* in1, float* q_out, int num_cu, void* stream);
+#ifdef EVG_BF16
+// the two networks' bf16 matrix-core forward (qnet_bf16_kernels.inc, libevg_bf16.so); validated by the caller as for the fp32 launches
+int launch_smart_qnet_bf16(const evg_qnet& net, int layout, long long rows, const float* in0, const float* in1, float* q_out, int num_cu, void* stream);
+int launch_minimized_qnet_bf16(const evg_mini_qnet& net, int layout, long long rows, const float* in0, const float* in1, float* q_out, int num_cu,
+                               void* stream);
+#endif
 // self-royale (population_kernels.inc); `pop` and the sizes are validated by the caller (evg_abi.hip)
 int launch_population_clear(const DevState& S, const evg_population& pop, void* stream);
 int launch_population_assign(const DevState& S, const evg_population& pop, const uint8_t* mask, const int8_t* winner, uint8_t* history, void* stream);

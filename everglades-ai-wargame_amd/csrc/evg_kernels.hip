@@ -83,6 +83,9 @@ namespace evg {
 #include "league_kernels.inc"   // the opponent league: clear, assign after an explicit reset, importance weights
 #include "minimized_qnet.inc"   // the Minimized agents' Q network's forward pass (59 -> h1 <= 128 -> 11) on v_mfma_f32_16x16x4_f32
 #include "population_kernels.inc"   // self-royale: per-env members drawn from a population, the bucket pass and the grouped Minimized forward
+#ifdef EVG_BF16                  // `make bf16` (libevg_bf16.so): the product's kernels plus ...
+#include "qnet_bf16_kernels.inc"    // the two Q networks' reduced-precision forward on v_mfma_f32_16x16x32_bf16 (acting, target network)
+#endif
 
 // ---------------------------------------------------------------------------------------------
 // launchers

@@ -260,3 +260,39 @@ class MinimizedQNet(SmartQNet):
     def _launch(self, d, layout, rows, in0, in1, out):
         return self.L.evg_minimized_qnet(self.env._h, C.byref(d), layout, rows, C.c_void_p(in0.data_ptr()),
                                          None if in1 is None else C.c_void_p(in1.data_ptr()), C.c_void_p(out.data_ptr()), self.env._stream())
+
+
+class _Bf16Launch(object):
+    """The bf16 matrix-core forward (include/evg_qnet_bf16.h, libevg_bf16.so) in place of the fp32 launch: the one thing the two classes below change.
+    A refused call's text is read from the library that refused it."""
+    _ENTRY = None
+
+    def _launch(self, d, layout, rows, in0, in1, out):
+        B = _lib.load_bf16()
+        rc = getattr(B, self._ENTRY)(self.env._h, C.byref(d), layout, rows, C.c_void_p(in0.data_ptr()),
+                                     None if in1 is None else C.c_void_p(in1.data_ptr()), C.c_void_p(out.data_ptr()), self.env._stream())
+        if rc:
+            _lib.check(rc, B)
+        return 0
+
+
+class SmartQNetBf16(_Bf16Launch, SmartQNet):
+    """SmartQNet with every layer on the bf16 matrix cores (evg_smart_qnet_bf16): inputs, weights and hidden activations rounded to bf16, fp32
+    accumulation and fp32 Q -- the numeric contract of include/evg_qnet_bf16.h, for acting and for the target network.  The same calls, checks and
+    parameter tracking; the fp32 parameters are read in place and converted on every call.  env.smart_qnet(net, precision="bf16") makes one."""
+    _ENTRY = "evg_smart_qnet_bf16"
+
+
+class MinimizedQNetBf16(_Bf16Launch, MinimizedQNet):
+    """MinimizedQNet with both layers on the bf16 matrix cores (evg_minimized_qnet_bf16); see SmartQNetBf16.
+    env.minimized_qnet(net, precision="bf16") makes one."""
+    _ENTRY = "evg_minimized_qnet_bf16"
+
+
+def make(env, net, final_relu, precision, fp32_cls, bf16_cls):
+    """the evaluator of env.smart_qnet / env.minimized_qnet for a precision: "fp32" (the bit-exact chain, the default) or "bf16" """
+    if precision == "fp32":
+        return fp32_cls(env, net, final_relu=final_relu)
+    if precision == "bf16":
+        return bf16_cls(env, net, final_relu=final_relu)
+    raise ValueError('precision must be "fp32" or "bf16" (got %r)' % (precision,))

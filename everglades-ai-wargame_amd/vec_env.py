@@ -584,13 +584,14 @@ class EvergladesVecEnv(object):
             self._check(rc)
         return out
 
-    def minimized_qnet(self, net, final_relu=None):
+    def minimized_qnet(self, net, final_relu=None, precision="fp32"):
         """The Minimized agents' Q network's forward pass on this env's device, one launch per call (everglades_amd.MinimizedQNet, evg_minimized_qnet):
         `net` is the reference's QNetwork(59, 11, fc1) (fc1 / fc2, final ReLU), an nn.Sequential Linear(59, h)/ReLU/Linear(h, 11)[/ReLU], a 4-tuple
         (w1, b1, w2, b2) with final_relu, or a pair of these (the two-seat layout); h in 1..128.  Its parameters are read in place on every call; the
-        output has no autograd."""
-        from .qnet import MinimizedQNet
-        return MinimizedQNet(self, net, final_relu=final_relu)
+        output has no autograd.  precision="bf16" returns a MinimizedQNetBf16: the same calls on the bf16 matrix cores (include/evg_qnet_bf16.h), for
+        acting and for the target network; "fp32" (the default) is the bit-exact chain."""
+        from . import qnet
+        return qnet.make(self, net, final_relu, precision, qnet.MinimizedQNet, qnet.MinimizedQNetBf16)
 
     def q_population(self, team0, team1=None, final_relu=None, max_rows=None):
         """Self-royale (everglades_amd.QPopulation; evg_population): two teams of Minimized Q networks, a member per env and seat drawn each episode --
@@ -620,12 +621,14 @@ class EvergladesVecEnv(object):
         return PrioritizedSmartReplay(self, capacity_turns, alpha=alpha, n_step=n_step, gamma=gamma, shaping=shaping, seats=seats,
                                       episode_base=episode_base)
 
-    def smart_qnet(self, net, final_relu=None):
+    def smart_qnet(self, net, final_relu=None, precision="fp32"):
         """The Smart_State Q network's forward pass on this env's device, one launch per call (everglades_amd.SmartQNet, evg_smart_qnet): `net` is the
         reference's QNetwork (final ReLU), an nn.Sequential Linear/ReLU/Linear/ReLU/Linear[/ReLU], a 6-tuple (w1, b1, w2, b2, w3, b3) with final_relu,
-        or a pair of these (the two-seat layout).  Its parameters are read in place on every call; the output has no autograd."""
-        from .qnet import SmartQNet
-        return SmartQNet(self, net, final_relu=final_relu)
+        or a pair of these (the two-seat layout).  Its parameters are read in place on every call; the output has no autograd.
+        precision="bf16" returns a SmartQNetBf16: the same calls on the bf16 matrix cores (include/evg_qnet_bf16.h), for acting and for the target
+        network; "fp32" (the default) is the bit-exact chain."""
+        from . import qnet
+        return qnet.make(self, net, final_relu, precision, qnet.SmartQNet, qnet.SmartQNetBf16)
 
     @staticmethod
     def expand_smart_state(shared, swarm):

@@ -48,12 +48,15 @@ def optimize_model(policy, target_eval, opt, batch):
     return loss.detach()
 
 
-def main(num_envs=8192, turns=300, batch=256, opponent="random_actions", seat=0, seed=1, epsilon=0.3, league=False):
+def main(num_envs=8192, turns=300, batch=256, opponent="random_actions", seat=0, seed=1, epsilon=0.3, league=False, acting_precision="fp32"):
     env = evg.EvergladesVecEnv(num_envs, seed=seed, auto_reset=True)
     policy, target = make_qnet(env.device, 0), make_qnet(env.device, 0)
     target.load_state_dict(policy.state_dict())
     opt = torch.optim.Adam(policy.parameters(), lr=LR)
-    act_net, target_eval = env.minimized_qnet(policy), env.minimized_qnet(target).expanded
+    # acting and the target network on the device; "bf16": both on the bf16 matrix cores (include/evg_qnet_bf16.h); the policy forward whose
+    # gradient the loss needs is torch's either way
+    act_net = env.minimized_qnet(policy, precision=acting_precision)
+    target_eval = env.minimized_qnet(target, precision=acting_precision).expanded
     mem = env.smart_replay(8, n_step=N_STEP, gamma=GAMMA, shaping="custom", seats=seat)
     env.reset()
     if league:
@@ -86,4 +89,13 @@ def main(num_envs=8192, turns=300, batch=256, opponent="random_actions", seat=0,
 
 if __name__ == "__main__":
     a = sys.argv[1:]
-    main(int(a[0]) if a else 8192, int(a[1]) if len(a) > 1 else 300, int(a[2]) if len(a) > 2 else 256, league=len(a) > 3 and a[3] in ("1", "league"))
+    precision = "fp32"                                    # --acting-precision {fp32,bf16}
+    for i, x in enumerate(a):
+        if x == "--acting-precision" or x.startswith("--acting-precision="):
+            precision = x.split("=", 1)[1] if "=" in x else a[i + 1]
+            del a[i:i + (1 if "=" in x else 2)]
+            break
+    if precision not in ("fp32", "bf16"):
+        sys.exit("--acting-precision must be fp32 or bf16")
+    main(int(a[0]) if a else 8192, int(a[1]) if len(a) > 1 else 300, int(a[2]) if len(a) > 2 else 256, league=len(a) > 3 and a[3] in ("1", "league"),
+         acting_precision=precision)

@@ -66,15 +66,19 @@ def optimize_model(policy, target, opt, batch, target_eval=None, weights=None):
     return loss.detach()
 
 
-def main(num_envs=8192, turns=300, batch=1024, opponent="swarm_agent", seat=0, seed=1, epsilon=0.3, device_net=False, prioritized=False):
+def main(num_envs=8192, turns=300, batch=1024, opponent="swarm_agent", seat=0, seed=1, epsilon=0.3, device_net=False, prioritized=False,
+         acting_precision="fp32"):
     env = evg.EvergladesVecEnv(num_envs, seed=seed, auto_reset=True)
     dev = env.device
     policy, target = make_qnet(dev, 0), make_qnet(dev, 0)
     target.load_state_dict(policy.state_dict())
     opt = torch.optim.Adam(policy.parameters(), lr=LR)
     act_net = target_eval = None
-    if device_net:
-        act_net, target_eval = env.smart_qnet(policy), env.smart_qnet(target).expanded
+    if device_net or acting_precision != "fp32":
+        # acting and the target network on the device; "bf16": both on the bf16 matrix cores (include/evg_qnet_bf16.h).  The policy forward whose
+        # gradient the loss needs stays in torch either way.
+        act_net = env.smart_qnet(policy, precision=acting_precision)
+        target_eval = env.smart_qnet(target, precision=acting_precision).expanded
     if prioritized:
         mem = env.prioritized_replay(8, alpha=0.6, n_step=N_STEP, gamma=GAMMA, shaping="reward_short_games", seats=seat)
     else:
@@ -111,5 +115,13 @@ def main(num_envs=8192, turns=300, batch=1024, opponent="swarm_agent", seat=0, s
 
 if __name__ == "__main__":
     a = [x for x in sys.argv[1:] if x != "--prioritized"]
+    precision = "fp32"                                    # --acting-precision {fp32,bf16} (implies the device network for bf16)
+    for i, x in enumerate(a):
+        if x == "--acting-precision" or x.startswith("--acting-precision="):
+            precision = x.split("=", 1)[1] if "=" in x else a[i + 1]
+            del a[i:i + (1 if "=" in x else 2)]
+            break
+    if precision not in ("fp32", "bf16"):
+        sys.exit("--acting-precision must be fp32 or bf16")
     main(int(a[0]) if a else 8192, int(a[1]) if len(a) > 1 else 300, int(a[2]) if len(a) > 2 else 1024, device_net=len(a) > 3 and a[3] in ("1", "device_net"),
-         prioritized="--prioritized" in sys.argv[1:])
+         prioritized="--prioritized" in sys.argv[1:], acting_precision=precision)
