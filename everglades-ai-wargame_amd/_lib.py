@@ -17,6 +17,11 @@ PRIORITY_EXPORTS = ["evg_replay_priority_clear", "evg_replay_update_priorities",
 # `make -C csrc bf16`: the product plus the two entry points of include/evg_qnet_bf16.h (SmartQNetBf16 / MinimizedQNetBf16 load it: load_bf16)
 BF16_LIB_PATH = os.path.join(HERE, "libevg_bf16.so")
 BF16_EXPORTS = ["evg_smart_qnet_bf16", "evg_minimized_qnet_bf16"]
+# `make -C csrc grad`: the product plus the two entry points of include/evg_qnet_grad.h (SmartQNet.with_grad / MinimizedQNet.with_grad load it: load_grad)
+GRAD_LIB_PATH = os.path.join(HERE, "libevg_grad.so")
+GRAD_EXPORTS = ["evg_smart_qnet_backward", "evg_minimized_qnet_backward"]
+# EVG_QNET_GRAD_MAX_BLOCKS, EVG_SMART_QNET_GRAD_PARTIAL, EVG_MINI_QNET_GRAD_PARTIAL (floats per workgroup) of include/evg_qnet_grad.h
+QNET_GRAD_MAX_BLOCKS, SMART_QNET_GRAD_PARTIAL, MINI_QNET_GRAD_PARTIAL = 512, 9360, 10384
 STAMPS_LIB_PATH = os.path.join(HERE, "libevg_stamps.so")  # `make -C csrc stamps`: in-kernel phase stamps (tools/stamps.py)
 
 NUM_PLAYERS, NUM_GROUPS, NUM_NODES, NUM_UNITS, NUM_ACTIONS, OBS_LEN = 2, 12, 11, 100, 7, 105
@@ -132,6 +137,17 @@ class EvgMiniQnet(C.Structure):
         ("struct_size", C.c_uint32), ("h1", C.c_int32), ("final_relu", C.c_int32), ("num_sets", C.c_int32),
         ("w1", C.c_void_p * 2), ("b1", C.c_void_p * 2), ("w2", C.c_void_p * 2), ("b2", C.c_void_p * 2),
     ]
+
+
+class EvgQnetGrads(C.Structure):
+    """evg_qnet_grads of include/evg_qnet_grad.h: where the Smart_State network's parameter gradients go (device pointers the caller owns)."""
+    _fields_ = [("struct_size", C.c_uint32), ("reserved", C.c_uint32), ("w1", C.c_void_p), ("b1", C.c_void_p), ("w2", C.c_void_p), ("b2", C.c_void_p),
+                ("w3", C.c_void_p), ("b3", C.c_void_p)]
+
+
+class EvgMiniQnetGrads(C.Structure):
+    """evg_mini_qnet_grads of include/evg_qnet_grad.h: where the Minimized network's parameter gradients go."""
+    _fields_ = [("struct_size", C.c_uint32), ("reserved", C.c_uint32), ("w1", C.c_void_p), ("b1", C.c_void_p), ("w2", C.c_void_p), ("b2", C.c_void_p)]
 
 
 class EvgLeague(C.Structure):
@@ -266,6 +282,9 @@ def load(path=None):
     if hasattr(L, "evg_smart_qnet_bf16"):            # libevg_bf16.so only
         L.evg_smart_qnet_bf16.argtypes = [vp, C.POINTER(EvgQnet), C.c_int, C.c_int64, vp, vp, vp, vp]
         L.evg_minimized_qnet_bf16.argtypes = [vp, C.POINTER(EvgMiniQnet), C.c_int, C.c_int64, vp, vp, vp, vp]
+    if hasattr(L, "evg_smart_qnet_backward"):        # libevg_grad.so only
+        L.evg_smart_qnet_backward.argtypes = [vp, C.POINTER(EvgQnet), C.c_int64, vp, vp, C.POINTER(EvgQnetGrads), vp, C.c_int64, C.c_float, vp]
+        L.evg_minimized_qnet_backward.argtypes = [vp, C.POINTER(EvgMiniQnet), C.c_int64, vp, vp, C.POINTER(EvgMiniQnetGrads), vp, C.c_int64, C.c_float, vp]
     lp = C.POINTER(EvgLeague)
     L.evg_league_clear.argtypes = [vp, lp, vp]
     L.evg_league_assign.argtypes = [vp, lp, vp, vp]
@@ -342,6 +361,16 @@ def load_bf16():
     missing = [n for n in BF16_EXPORTS if not hasattr(L, n)]
     if missing:
         raise EvgError("%s does not export %s; rebuild it (make -C everglades-ai-wargame_amd/csrc bf16)" % (BF16_LIB_PATH, ", ".join(missing)))
+    return L
+
+
+def load_grad():
+    """Load libevg_grad.so: libevg.so's sources built with -DEVG_GRAD, which exports the entry points of include/evg.h plus GRAD_EXPORTS
+    (include/evg_qnet_grad.h).  A handle of libevg.so is valid in it; a failed call's text is its own evg_last_error (check(rc, this library))."""
+    L = load(GRAD_LIB_PATH)
+    missing = [n for n in GRAD_EXPORTS if not hasattr(L, n)]
+    if missing:
+        raise EvgError("%s does not export %s; rebuild it (make -C everglades-ai-wargame_amd/csrc grad)" % (GRAD_LIB_PATH, ", ".join(missing)))
     return L
 
 

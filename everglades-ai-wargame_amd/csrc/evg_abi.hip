@@ -1002,9 +1002,9 @@ int evg_replay_sample_prioritized(evg_handle* h, const evg_replay* m, int batch,
 
 // ---- the Smart_State Q network (include/evg.h, evg_smart_qnet) ----
 // (the checks of evg_smart_qnet and, in libevg_bf16.so, of evg_smart_qnet_bf16: the same refusals, then the entry point's own launch)
+// (... and, in libevg_grad.so, of evg_smart_qnet_backward, whose x and gq stand for in0 and q_out)
 typedef int (*smart_qnet_launch)(const evg_qnet&, int, long long, const float*, const float*, float*, int, void*);
-static int smart_qnet_call(evg_handle* h, const evg_qnet* net, int layout, int64_t rows, const float* in0, const float* in1, float* q_out, void* stream,
-                           smart_qnet_launch launch) {
+static int smart_qnet_check(evg_handle* h, const evg_qnet* net, int layout, int64_t rows, const float* in0, const float* in1, const float* q_out) {
     if (!h || !net) return fail(EVG_ERR_INVALID, "null handle or network descriptor");
     if (net->struct_size != sizeof(evg_qnet)) return fail(EVG_ERR_INVALID, "qnet: struct_size %u != sizeof(evg_qnet) %zu", net->struct_size, sizeof(evg_qnet));
     if (net->h1 < 1 || net->h1 > EVG_QNET_MAX_HIDDEN || net->h2 < 1 || net->h2 > EVG_QNET_MAX_HIDDEN)
@@ -1025,6 +1025,12 @@ static int smart_qnet_call(evg_handle* h, const evg_qnet* net, int layout, int64
     }
     if (!in0 || !q_out || (layout != EVG_QNET_EXPANDED && !in1)) return fail(EVG_ERR_INVALID, "qnet: in0, q_out and (compact layouts) in1 are required");
     EVG_NEED_ALIGNED16(in0); EVG_NEED_ALIGNED16(in1); EVG_NEED_ALIGNED16(q_out);
+    return EVG_OK;
+}
+
+static int smart_qnet_call(evg_handle* h, const evg_qnet* net, int layout, int64_t rows, const float* in0, const float* in1, float* q_out, void* stream,
+                           smart_qnet_launch launch) {
+    { const int rc = smart_qnet_check(h, net, layout, rows, in0, in1, q_out); if (rc) return rc; }
     EVG_ON_DEVICE(h);
     return launched("qnet", launch(*net, layout, (long long)rows, in0, in1, q_out, h->caps.cus, stream));
 }
@@ -1036,6 +1042,39 @@ int evg_smart_qnet(evg_handle* h, const evg_qnet* net, int layout, int64_t rows,
 #ifdef EVG_BF16     // include/evg_qnet_bf16.h; libevg_bf16.so only
 int evg_smart_qnet_bf16(evg_handle* h, const evg_qnet* net, int layout, int64_t rows, const float* in0, const float* in1, float* q_out, void* stream) try {
     return smart_qnet_call(h, net, layout, rows, in0, in1, q_out, stream, launch_smart_qnet_bf16);
+} catch (...) { return on_exception(); }
+#endif
+
+#ifdef EVG_GRAD     // include/evg_qnet_grad.h; libevg_grad.so only
+// what the two backward entry points refuse beyond the per-network check: the gradient pointers, the workspace, the clamp
+static int qnet_grad_check(evg_handle* h, int64_t rows, float* const* grads, const char* const* names, int count, const void* workspace,
+                           int64_t workspace_bytes, int64_t partial_floats, float clamp) {
+    for (int i = 0; i < count; ++i) {
+        if (!grads[i]) return fail(EVG_ERR_INVALID, "qnet backward: the gradient pointer %s is NULL", names[i]);
+        if (misaligned16(grads[i])) return fail(EVG_ERR_INVALID, "qnet backward: the gradient pointer %s must be 16-byte aligned (got %p)", names[i], (const void*)grads[i]);
+    }
+    if (!workspace) return fail(EVG_ERR_INVALID, "qnet backward: the workspace is NULL");
+    EVG_NEED_ALIGNED16(workspace);
+    const int64_t need = 4 * partial_floats * (int64_t)qnet_grad_blocks((long long)rows, h->caps.cus);
+    if (workspace_bytes < need)
+        return fail(EVG_ERR_INVALID, "qnet backward: the workspace is too small (%lld bytes, %lld rows need %lld)", (long long)workspace_bytes, (long long)rows, (long long)need);
+    if (!(clamp >= 0.0f) || clamp > 3.402823466e+38f) return fail(EVG_ERR_INVALID, "qnet backward: clamp must be finite and >= 0 (got %g)", (double)clamp);
+    return EVG_OK;
+}
+
+int evg_smart_qnet_backward(evg_handle* h, const evg_qnet* net, int64_t rows, const float* x, const float* gq, const evg_qnet_grads* grads,
+                            void* workspace, int64_t workspace_bytes, float clamp, void* stream) try {
+    if (net && net->struct_size == sizeof(evg_qnet) && net->num_sets != 1)
+        return fail(EVG_ERR_INVALID, "qnet backward: one network only (got num_sets %d)", net->num_sets);
+    { const int rc = smart_qnet_check(h, net, EVG_QNET_EXPANDED, rows, x, nullptr, gq); if (rc) return rc; }
+    if (!grads) return fail(EVG_ERR_INVALID, "qnet backward: null gradient descriptor");
+    if (grads->struct_size != sizeof(evg_qnet_grads))
+        return fail(EVG_ERR_INVALID, "qnet backward: struct_size %u != sizeof(evg_qnet_grads) %zu", grads->struct_size, sizeof(evg_qnet_grads));
+    float* const g[6] = {grads->w1, grads->b1, grads->w2, grads->b2, grads->w3, grads->b3};
+    static const char* const names[6] = {"w1", "b1", "w2", "b2", "w3", "b3"};
+    { const int rc = qnet_grad_check(h, rows, g, names, 6, workspace, workspace_bytes, EVG_SMART_QNET_GRAD_PARTIAL, clamp); if (rc) return rc; }
+    EVG_ON_DEVICE(h);
+    return launched("qnet backward", launch_smart_qnet_backward(*net, (long long)rows, x, gq, *grads, static_cast<float*>(workspace), clamp, h->caps.cus, stream));
 } catch (...) { return on_exception(); }
 #endif
 
@@ -1237,9 +1276,9 @@ int evg_step_league_minimized_q(evg_handle* h, const float* q, float epsilon0, f
 } catch (...) { return on_exception(); }
 
 // (the checks of evg_minimized_qnet and, in libevg_bf16.so, of evg_minimized_qnet_bf16: the same refusals, then the entry point's own launch)
+// (... and, in libevg_grad.so, of evg_minimized_qnet_backward, whose x and gq stand for in0 and q_out)
 typedef int (*mini_qnet_launch)(const evg_mini_qnet&, int, long long, const float*, const float*, float*, int, void*);
-static int minimized_qnet_call(evg_handle* h, const evg_mini_qnet* net, int layout, int64_t rows, const float* in0, const float* in1, float* q_out,
-                               void* stream, mini_qnet_launch launch) {
+static int minimized_qnet_check(evg_handle* h, const evg_mini_qnet* net, int layout, int64_t rows, const float* in0, const float* in1, const float* q_out) {
     if (!h || !net) return fail(EVG_ERR_INVALID, "null handle or network descriptor");
     if (net->struct_size != sizeof(evg_mini_qnet))
         return fail(EVG_ERR_INVALID, "minimized qnet: struct_size %u != sizeof(evg_mini_qnet) %zu", net->struct_size, sizeof(evg_mini_qnet));
@@ -1262,6 +1301,12 @@ static int minimized_qnet_call(evg_handle* h, const evg_mini_qnet* net, int layo
     if (!in0 || !q_out || (layout != EVG_QNET_EXPANDED && !in1))
         return fail(EVG_ERR_INVALID, "minimized qnet: in0, q_out and (compact layouts) in1 are required");
     EVG_NEED_ALIGNED16(in0); EVG_NEED_ALIGNED16(in1); EVG_NEED_ALIGNED16(q_out);
+    return EVG_OK;
+}
+
+static int minimized_qnet_call(evg_handle* h, const evg_mini_qnet* net, int layout, int64_t rows, const float* in0, const float* in1, float* q_out,
+                               void* stream, mini_qnet_launch launch) {
+    { const int rc = minimized_qnet_check(h, net, layout, rows, in0, in1, q_out); if (rc) return rc; }
     EVG_ON_DEVICE(h);
     return launched("minimized qnet", launch(*net, layout, (long long)rows, in0, in1, q_out, h->caps.cus, stream));
 }
@@ -1274,6 +1319,24 @@ int evg_minimized_qnet(evg_handle* h, const evg_mini_qnet* net, int layout, int6
 int evg_minimized_qnet_bf16(evg_handle* h, const evg_mini_qnet* net, int layout, int64_t rows, const float* in0, const float* in1, float* q_out,
                             void* stream) try {
     return minimized_qnet_call(h, net, layout, rows, in0, in1, q_out, stream, launch_minimized_qnet_bf16);
+} catch (...) { return on_exception(); }
+#endif
+
+#ifdef EVG_GRAD     // include/evg_qnet_grad.h; libevg_grad.so only
+int evg_minimized_qnet_backward(evg_handle* h, const evg_mini_qnet* net, int64_t rows, const float* x, const float* gq, const evg_mini_qnet_grads* grads,
+                                void* workspace, int64_t workspace_bytes, float clamp, void* stream) try {
+    if (net && net->struct_size == sizeof(evg_mini_qnet) && net->num_sets != 1)
+        return fail(EVG_ERR_INVALID, "qnet backward: one network only (got num_sets %d)", net->num_sets);
+    { const int rc = minimized_qnet_check(h, net, EVG_QNET_EXPANDED, rows, x, nullptr, gq); if (rc) return rc; }
+    if (!grads) return fail(EVG_ERR_INVALID, "qnet backward: null gradient descriptor");
+    if (grads->struct_size != sizeof(evg_mini_qnet_grads))
+        return fail(EVG_ERR_INVALID, "qnet backward: struct_size %u != sizeof(evg_mini_qnet_grads) %zu", grads->struct_size, sizeof(evg_mini_qnet_grads));
+    float* const g[4] = {grads->w1, grads->b1, grads->w2, grads->b2};
+    static const char* const names[4] = {"w1", "b1", "w2", "b2"};
+    { const int rc = qnet_grad_check(h, rows, g, names, 4, workspace, workspace_bytes, EVG_MINI_QNET_GRAD_PARTIAL, clamp); if (rc) return rc; }
+    EVG_ON_DEVICE(h);
+    return launched("minimized qnet backward",
+                    launch_minimized_qnet_backward(*net, (long long)rows, x, gq, *grads, static_cast<float*>(workspace), clamp, h->caps.cus, stream));
 } catch (...) { return on_exception(); }
 #endif
 

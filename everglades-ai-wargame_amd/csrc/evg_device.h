@@ -29,6 +29,9 @@
 #ifdef EVG_BF16
 #include "../../include/evg_qnet_bf16.h"
 #endif
+#ifdef EVG_GRAD
+#include "../../include/evg_qnet_grad.h"
+#endif
 #include "evg_rng.h"
 
 namespace evg {
@@ -265,6 +268,15 @@ int launch_minimized_qnet(const evg_mini_qnet& net, int layout, long long rows, 
 int launch_smart_qnet_bf16(const evg_qnet& net, int layout, long long rows, const float* in0, const float* in1, float* q_out, int num_cu, void* stream);
 int launch_minimized_qnet_bf16(const evg_mini_qnet& net, int layout, long long rows, const float* in0, const float* in1, float* q_out, int num_cu,
                                void* stream);
+#endif
+#ifdef EVG_GRAD
+// the backward pass of the two networks' expanded forward (qnet_grad_kernels.inc, libevg_grad.so); validated by the caller.  qnet_grad_blocks: the
+// workgroups of a launch, each of which leaves one partial in the workspace
+long long qnet_grad_blocks(long long rows, int num_cu);
+int launch_smart_qnet_backward(const evg_qnet& net, long long rows, const float* x, const float* gq, const evg_qnet_grads& out, float* workspace,
+                               float clamp, int num_cu, void* stream);
+int launch_minimized_qnet_backward(const evg_mini_qnet& net, long long rows, const float* x, const float* gq, const evg_mini_qnet_grads& out,
+                                   float* workspace, float clamp, int num_cu, void* stream);
 #endif
 // self-royale (population_kernels.inc); `pop` and the sizes are validated by the caller (evg_abi.hip)
 int launch_population_clear(const DevState& S, const evg_population& pop, void* stream);

@@ -3,13 +3,15 @@
 An inference evaluator for the reference's QNetwork shape (agents/Smart_State/QNetwork.py: relu(fc3(relu(fc2(relu(fc1(x))))))), 59 -> h1 -> h2 -> 5 with
 h1, h2 in 1..64.  The network stays the consumer's: the evaluator reads its fp32 parameters in place on every call, so optimizer.step() and
 load_state_dict take effect without rebinding, and a module whose parameters were replaced (not updated in place) is followed too.  Training stays in
-torch: the output is a plain tensor without autograd, so optimize_model's policy forward (whose gradient the loss needs) stays a torch forward; the
-target network's forward and the acting turn's forward can use the evaluator.
+torch: the output of a call is a plain tensor without autograd, for the target network's forward and the acting turn's forward; optimize_model's
+policy forward (whose gradient the loss needs) is a torch forward, or qnet.with_grad(x): the same values with the device's backward pass behind them
+(include/evg_qnet_grad.h; the loss, the clamp of the summed gradients and the optimizer stay the consumer's).
 
     qnet = env.smart_qnet(policy_net)                     # QNetwork (final ReLU), nn.Sequential(Linear, ReLU, Linear, ReLU, Linear[, ReLU]),
                                                           # a 6-tuple (w1, b1, w2, b2, w3, b3) with final_relu=..., or a pair of these (two seats)
     q = qnet(shared, swarm)                               # [N, 34], [N, 12, 13] -> [N, 12, 5];  [N, 2, 34], [N, 2, 12, 13] -> [N, 2, 12, 5]
     q = qnet.expanded(x)                                  # [..., 59] -> [..., 5]
+    q = qnet.with_grad(x)                                 # ... carrying autograd: loss(q.gather(1, a), y).backward() fills the parameters' .grad
 
 Numerics: every pre-activation is the fmaf chain b[j], then k ascending (include/evg.h); the compact and the expanded forms of the same features give
 equal Q.  No host synchronisation and no allocation when `out` is given: a call can sit inside a captured torch.cuda.graph.
@@ -175,6 +177,81 @@ class SmartQNet(object):
             self._input(out, shape, "out")
         return self._run(_lib.QNET_EXPANDED, 1, rows, x, None, out)
 
+    # ---- the differentiable form (include/evg_qnet_grad.h, libevg_grad.so)
+    _GRAD_ENTRY, _GRAD_STRUCT, _GRAD_PARTIAL = "evg_smart_qnet_backward", _lib.EvgQnetGrads, _lib.SMART_QNET_GRAD_PARTIAL
+
+    def with_grad(self, x, clamp=None):
+        """expanded(x) carrying autograd: x [..., 59] -> [..., OUT], the same values bit for bit, whose backward() is the device's backward pass
+        (evg_smart_qnet_backward / evg_minimized_qnet_backward: two launches) and leaves the gradients of the network's parameters -- the tensors
+        the module holds at this call -- in their .grad, as a torch forward would; x gets none.  `clamp` (None, or c > 0) clamps every element of
+        the gradients this call contributes to [-c, c].  One network only; the fp32 classes only."""
+        torch = _torch()
+        if self.pair:
+            raise ValueError("with_grad() differentiates one network, not a pair")
+        if not isinstance(x, torch.Tensor) or x.dim() < 1 or x.shape[-1] != 59:
+            raise ValueError("x must be a float32 tensor [..., 59]")
+        if x.requires_grad:
+            raise ValueError("with_grad() has no gradient with respect to x: x must not require grad")
+        if clamp is not None and not (isinstance(clamp, (int, float)) and 0.0 < float(clamp) < float("inf")):
+            raise ValueError("clamp must be None or a finite number > 0 (got %r)" % (clamp,))
+        self._input(x, tuple(x.shape), "x")
+        ts, _ = self._params(0)
+        return _grad_function()(self, 0.0 if clamp is None else float(clamp), x, *ts)
+
+    def _backward(self, x, ts, gq, clamp):
+        """the gradients of ts (the parameters saved by with_grad's forward) for the upstream gradient gq [..., OUT]: new tensors of their shapes"""
+        torch = _torch()
+        G = _lib.load_grad()
+        rows = x.numel() // 59
+        gq = gq.to(torch.float32).contiguous()
+        self._input(gq, tuple(x.shape[:-1]) + (self.OUT,), "the upstream gradient")
+        if getattr(self, "_grad_ws", None) is None:                     # one partial per workgroup of the largest grid, allocated once
+            self._grad_ws = torch.empty(_lib.QNET_GRAD_MAX_BLOCKS * self._GRAD_PARTIAL, dtype=torch.float32, device=self.env.device)
+        d = type(self._d)()
+        d.struct_size = C.sizeof(d)
+        names = [n for n, _ in self._GRAD_STRUCT._fields_[2:]]
+        grads = [torch.empty_like(t, memory_format=torch.contiguous_format) for t in ts]
+        gs = self._GRAD_STRUCT()
+        gs.struct_size = C.sizeof(gs)
+        for n, t, g in zip(names, ts, grads):
+            getattr(d, n)[0] = t.data_ptr()
+            setattr(gs, n, g.data_ptr())
+        d.h1, d.final_relu, d.num_sets = ts[0].shape[0], int(self.final_relu), 1
+        if hasattr(d, "h2"):
+            d.h2 = ts[2].shape[0]
+        rc = getattr(G, self._GRAD_ENTRY)(self.env._h, C.byref(d), rows, C.c_void_p(x.data_ptr()), C.c_void_p(gq.data_ptr()), C.byref(gs),
+                                          C.c_void_p(self._grad_ws.data_ptr()), self._grad_ws.numel() * 4, clamp, self.env._stream())
+        if rc:
+            _lib.check(rc, G)
+        return grads
+
+
+_GRAD_FN = []
+
+
+def _grad_function():
+    """the torch.autograd.Function behind with_grad (made on first use: importing this module does not import torch)"""
+    if _GRAD_FN:
+        return _GRAD_FN[0]
+    torch = _torch()
+    from torch.autograd.function import once_differentiable
+
+    class QNetWithGrad(torch.autograd.Function):
+        @staticmethod
+        def forward(ctx, net, clamp, x, *params):
+            ctx.net, ctx.clamp = net, clamp
+            ctx.save_for_backward(x, *params)
+            return net.expanded(x)
+
+        @staticmethod
+        @once_differentiable
+        def backward(ctx, gq):
+            x, params = ctx.saved_tensors[0], ctx.saved_tensors[1:]
+            return (None, None, None) + tuple(ctx.net._backward(x, params, gq, ctx.clamp))
+
+    _GRAD_FN.append(QNetWithGrad.apply)
+    return _GRAD_FN[0]
+
 
 def _mini_param_source(net, final_relu):
     """-> (a function returning the 4 tensors as they are now, final_relu)."""
@@ -257,6 +334,8 @@ class MinimizedQNet(SmartQNet):
         d.h1, d.final_relu, d.num_sets = self.h1, int(self.final_relu), sets
         return d
 
+    _GRAD_ENTRY, _GRAD_STRUCT, _GRAD_PARTIAL = "evg_minimized_qnet_backward", _lib.EvgMiniQnetGrads, _lib.MINI_QNET_GRAD_PARTIAL
+
     def _launch(self, d, layout, rows, in0, in1, out):
         return self.L.evg_minimized_qnet(self.env._h, C.byref(d), layout, rows, C.c_void_p(in0.data_ptr()),
                                          None if in1 is None else C.c_void_p(in1.data_ptr()), C.c_void_p(out.data_ptr()), self.env._stream())
@@ -266,6 +345,9 @@ class _Bf16Launch(object):
     """The bf16 matrix-core forward (include/evg_qnet_bf16.h, libevg_bf16.so) in place of the fp32 launch: the one thing the two classes below change.
     A refused call's text is read from the library that refused it."""
     _ENTRY = None
+
+    def with_grad(self, x, clamp=None):
+        raise ValueError("with_grad() is defined on the fp32 chain: use the fp32 evaluator (precision=\"fp32\") for the policy forward")
 
     def _launch(self, d, layout, rows, in0, in1, out):
         B = _lib.load_bf16()

@@ -8,9 +8,11 @@ DQNAgent.py:300, through shaping="custom"), optimize_model fed by SmartReplay.sa
              --evg_replay_record--> n-step sums --evg_replay_sample--> swarm_obs, action, next_state_swarms, reward, not_done --optimize_model (torch)--> loss
 
 The acting forward and the target network's forward run as one launch each (env.minimized_qnet: the modules' parameters are read in place); the policy
-forward inside optimize_model stays torch (its gradient is the loss's).  A DQN loss need not decrease.
+forward inside optimize_model is torch's (its gradient is the loss's) or, with --device-backward, MinimizedQNet.with_grad: the fp32 evaluator's
+forward with the device's backward pass behind it (include/evg_qnet_grad.h); the loss, the clamp and Adam are torch's either way.  A DQN loss need
+not decrease.
 
-    python examples/minimized_training.py [envs] [turns] [batch] [league]
+    python examples/minimized_training.py [envs] [turns] [batch] [league] [--device-backward]
 """
 import os
 import sys
@@ -32,9 +34,10 @@ def make_qnet(device, seed=0):
     return torch.nn.Sequential(torch.nn.Linear(59, FC1), torch.nn.ReLU(), torch.nn.Linear(FC1, 11), torch.nn.ReLU()).to(device)
 
 
-def optimize_model(policy, target_eval, opt, batch):
+def optimize_model(policy, target_eval, opt, batch, policy_forward=None):
+    """policy_forward: the policy network's differentiable forward on the device (MinimizedQNet.with_grad) in place of the module's own"""
     swarm_obs, action, next_state, reward, not_done = batch
-    predicted = policy(swarm_obs).gather(1, action.unsqueeze(1))
+    predicted = (policy if policy_forward is None else policy_forward)(swarm_obs).gather(1, action.unsqueeze(1))
     with torch.no_grad():
         nxt = target_eval(next_state)                                                      # [B, 12, 11]
         nxt = torch.where(not_done[:, None, None], nxt, torch.zeros_like(nxt))
@@ -48,15 +51,17 @@ def optimize_model(policy, target_eval, opt, batch):
     return loss.detach()
 
 
-def main(num_envs=8192, turns=300, batch=256, opponent="random_actions", seat=0, seed=1, epsilon=0.3, league=False, acting_precision="fp32"):
+def main(num_envs=8192, turns=300, batch=256, opponent="random_actions", seat=0, seed=1, epsilon=0.3, league=False, acting_precision="fp32",
+         device_backward=False):
     env = evg.EvergladesVecEnv(num_envs, seed=seed, auto_reset=True)
     policy, target = make_qnet(env.device, 0), make_qnet(env.device, 0)
     target.load_state_dict(policy.state_dict())
     opt = torch.optim.Adam(policy.parameters(), lr=LR)
     # acting and the target network on the device; "bf16": both on the bf16 matrix cores (include/evg_qnet_bf16.h); the policy forward whose
-    # gradient the loss needs is torch's either way
+    # gradient the loss needs is torch's, or (device_backward) the fp32 evaluator's with_grad: the gradient is defined on the fp32 chain
     act_net = env.minimized_qnet(policy, precision=acting_precision)
     target_eval = env.minimized_qnet(target, precision=acting_precision).expanded
+    policy_forward = env.minimized_qnet(policy).with_grad if device_backward else None
     mem = env.smart_replay(8, n_step=N_STEP, gamma=GAMMA, shaping="custom", seats=seat)
     env.reset()
     if league:
@@ -70,7 +75,7 @@ def main(num_envs=8192, turns=300, batch=256, opponent="random_actions", seat=0,
         env.step_vs_q(opponent, q, epsilon, seat=seat, features=mem.slot_features(t + 1), actions_out=mem.slot_directions(t))
         mem.record(shaped=(env.reward[:, seat] / 10000.0).contiguous())
         if t >= N_STEP + 1:
-            losses.append(optimize_model(policy, target_eval, opt, mem.sample(batch, seed=seed)))
+            losses.append(optimize_model(policy, target_eval, opt, mem.sample(batch, seed=seed), policy_forward))
         if t % 100 == 99:
             target.load_state_dict(policy.state_dict())
             if league:
@@ -81,14 +86,15 @@ def main(num_envs=8192, turns=300, batch=256, opponent="random_actions", seat=0,
     mem.check()
     assert int(mem.size().item()) > 0
     print("%d envs x %d turns in %.3f s (%.1f M env-steps/s, network and learning included); memory holds %d transitions; loss first %.4g last %.4g, "
-          "all finite: %s" % (num_envs, turns, dt, num_envs * turns / dt / 1e6, int(mem.size().item()), float(losses[0]), float(losses[-1]),
-                               bool(torch.isfinite(losses).all())))
+          "all finite: %s%s" % (num_envs, turns, dt, num_envs * turns / dt / 1e6, int(mem.size().item()), float(losses[0]), float(losses[-1]),
+                               bool(torch.isfinite(losses).all()), "; policy forward with the device backward" if device_backward else ""))
+    assert bool(torch.isfinite(losses).all())
     env.close()
     return losses
 
 
 if __name__ == "__main__":
-    a = sys.argv[1:]
+    a = [x for x in sys.argv[1:] if x != "--device-backward"]
     precision = "fp32"                                    # --acting-precision {fp32,bf16}
     for i, x in enumerate(a):
         if x == "--acting-precision" or x.startswith("--acting-precision="):
@@ -98,4 +104,4 @@ if __name__ == "__main__":
     if precision not in ("fp32", "bf16"):
         sys.exit("--acting-precision must be fp32 or bf16")
     main(int(a[0]) if a else 8192, int(a[1]) if len(a) > 1 else 300, int(a[2]) if len(a) > 2 else 256, league=len(a) > 3 and a[3] in ("1", "league"),
-         acting_precision=precision)
+         acting_precision=precision, device_backward="--device-backward" in sys.argv[1:])

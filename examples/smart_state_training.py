@@ -12,12 +12,13 @@ over swarms of the best target-network Q of the next state, times gamma ** n_ste
 
 With device_net=True the acting forward (policy on the compact features) and the target network's forward on sample()'s next_state_swarms run as
 one launch each (env.smart_qnet, evg_smart_qnet: the modules' parameters read in place, so Adam's steps and load_state_dict are seen); the policy
-forward inside optimize_model stays torch (its gradient is the loss's).
+forward inside optimize_model is torch's (its gradient is the loss's) or, with --device-backward, SmartQNet.with_grad: the fp32 evaluator's forward
+with the device's backward pass behind it (include/evg_qnet_grad.h).  The loss, the clamp and Adam are torch's either way.
 
 With --prioritized the memory is env.prioritized_replay (agents/DQN/PrioritizedMemory.py: alpha 0.6, beta 0.4): the batch is drawn by priority, the
 Huber loss is weighted per sample by the importance weights and |td| + 1e-5 goes back as the new priorities (evg_replay_update_priorities).
 
-    python examples/smart_state_training.py [envs] [turns] [batch] [device_net] [--prioritized]
+    python examples/smart_state_training.py [envs] [turns] [batch] [device_net] [--prioritized] [--device-backward]
 """
 import os
 import sys
@@ -41,12 +42,13 @@ def q_values(net, shared, swarm):
     return net(evg.EvergladesVecEnv.expand_smart_state(shared, swarm)).contiguous()
 
 
-def optimize_model(policy, target, opt, batch, target_eval=None, weights=None):
+def optimize_model(policy, target, opt, batch, target_eval=None, weights=None, policy_forward=None):
     """DQNAgent.optimize_model (DQNAgent.py:336-385) on the sampled operands.  target_eval: the target network on the device (SmartQNet.expanded).
     weights: importance weights [B] of a prioritized batch -- the loss is then the weighted mean of the per-sample Huber terms and the call returns
-    (loss, new priorities |td| + 1e-5)."""
+    (loss, new priorities |td| + 1e-5).  policy_forward: the policy network's differentiable forward on the device (SmartQNet.with_grad) in place of
+    the module's own."""
     swarm_obs, action, next_state, reward, not_done = batch
-    predicted = policy(swarm_obs).gather(1, action.unsqueeze(1))
+    predicted = (policy if policy_forward is None else policy_forward)(swarm_obs).gather(1, action.unsqueeze(1))
     with torch.no_grad():
         nxt = target(next_state) if target_eval is None else target_eval(next_state)                                       # [B, 12, 5]; zeros rows where not_done is False give Q of zeros: mask below
         nxt = torch.where(not_done[:, None, None], nxt, torch.zeros_like(nxt))
@@ -67,7 +69,7 @@ def optimize_model(policy, target, opt, batch, target_eval=None, weights=None):
 
 
 def main(num_envs=8192, turns=300, batch=1024, opponent="swarm_agent", seat=0, seed=1, epsilon=0.3, device_net=False, prioritized=False,
-         acting_precision="fp32"):
+         acting_precision="fp32", device_backward=False):
     env = evg.EvergladesVecEnv(num_envs, seed=seed, auto_reset=True)
     dev = env.device
     policy, target = make_qnet(dev, 0), make_qnet(dev, 0)
@@ -76,9 +78,10 @@ def main(num_envs=8192, turns=300, batch=1024, opponent="swarm_agent", seat=0, s
     act_net = target_eval = None
     if device_net or acting_precision != "fp32":
         # acting and the target network on the device; "bf16": both on the bf16 matrix cores (include/evg_qnet_bf16.h).  The policy forward whose
-        # gradient the loss needs stays in torch either way.
+        # gradient the loss needs is torch's, or (device_backward) the fp32 evaluator's with_grad: the gradient is defined on the fp32 chain.
         act_net = env.smart_qnet(policy, precision=acting_precision)
         target_eval = env.smart_qnet(target, precision=acting_precision).expanded
+    policy_forward = env.smart_qnet(policy).with_grad if device_backward else None
     if prioritized:
         mem = env.prioritized_replay(8, alpha=0.6, n_step=N_STEP, gamma=GAMMA, shaping="reward_short_games", seats=seat)
     else:
@@ -95,11 +98,11 @@ def main(num_envs=8192, turns=300, batch=1024, opponent="swarm_agent", seat=0, s
         mem.record()
         if t >= N_STEP + 1 and prioritized:
             out = mem.sample(batch, seed=seed, beta=0.4)
-            loss, priorities = optimize_model(policy, target, opt, out[:5], target_eval, weights=out[5])
+            loss, priorities = optimize_model(policy, target, opt, out[:5], target_eval, weights=out[5], policy_forward=policy_forward)
             mem.update_priorities(out[6], priorities)
             losses.append(loss)
         elif t >= N_STEP + 1:
-            losses.append(optimize_model(policy, target, opt, mem.sample(batch, seed=seed), target_eval))
+            losses.append(optimize_model(policy, target, opt, mem.sample(batch, seed=seed), target_eval, policy_forward=policy_forward))
         if t % 100 == 99:
             target.load_state_dict(policy.state_dict())
     torch.cuda.synchronize()
@@ -107,14 +110,15 @@ def main(num_envs=8192, turns=300, batch=1024, opponent="swarm_agent", seat=0, s
     losses = torch.stack(losses).cpu()
     mem.check()
     print("%d envs x %d turns in %.3f s (%.1f M env-steps/s, network and learning included); memory holds %d transitions; loss first %.4g last %.4g, "
-          "all finite: %s" % (num_envs, turns, dt, num_envs * turns / dt / 1e6, int(mem.size().item()), float(losses[0]), float(losses[-1]),
-                               bool(torch.isfinite(losses).all())))
+          "all finite: %s%s" % (num_envs, turns, dt, num_envs * turns / dt / 1e6, int(mem.size().item()), float(losses[0]), float(losses[-1]),
+                               bool(torch.isfinite(losses).all()), "; policy forward with the device backward" if device_backward else ""))
+    assert bool(torch.isfinite(losses).all())
     env.close()
     return losses
 
 
 if __name__ == "__main__":
-    a = [x for x in sys.argv[1:] if x != "--prioritized"]
+    a = [x for x in sys.argv[1:] if x not in ("--prioritized", "--device-backward")]
     precision = "fp32"                                    # --acting-precision {fp32,bf16} (implies the device network for bf16)
     for i, x in enumerate(a):
         if x == "--acting-precision" or x.startswith("--acting-precision="):
@@ -124,4 +128,4 @@ if __name__ == "__main__":
     if precision not in ("fp32", "bf16"):
         sys.exit("--acting-precision must be fp32 or bf16")
     main(int(a[0]) if a else 8192, int(a[1]) if len(a) > 1 else 300, int(a[2]) if len(a) > 2 else 1024, device_net=len(a) > 3 and a[3] in ("1", "device_net"),
-         prioritized="--prioritized" in sys.argv[1:], acting_precision=precision)
+         prioritized="--prioritized" in sys.argv[1:], acting_precision=precision, device_backward="--device-backward" in sys.argv[1:])
