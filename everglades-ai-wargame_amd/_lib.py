@@ -22,7 +22,13 @@ GRAD_LIB_PATH = os.path.join(HERE, "libevg_grad.so")
 GRAD_EXPORTS = ["evg_smart_qnet_backward", "evg_minimized_qnet_backward"]
 # EVG_QNET_GRAD_MAX_BLOCKS, EVG_SMART_QNET_GRAD_PARTIAL, EVG_MINI_QNET_GRAD_PARTIAL (floats per workgroup) of include/evg_qnet_grad.h
 QNET_GRAD_MAX_BLOCKS, SMART_QNET_GRAD_PARTIAL, MINI_QNET_GRAD_PARTIAL = 512, 9360, 10384
-STAMPS_LIB_PATH = os.path.join(HERE, "libevg_stamps.so")  # `make -C csrc stamps`: in-kernel phase stamps (tools/stamps.py)
+# `make -C csrc learn`: the product plus GRAD_EXPORTS plus the two entry points of include/evg_learn.h (DqnLearner loads it: load_learn)
+LEARN_LIB_PATH = os.path.join(HERE, "libevg_learn.so")
+LEARN_EXPORTS = ["evg_td_head", "evg_adam_step"]
+# EVG_TD_* modes, EVG_TD_HEAD_WORKSPACE_BYTES, EVG_TD_HEAD_MAX_BATCH, EVG_ADAM_MAX_TENSORS, EVG_ADAM_CTL_BYTES of include/evg_learn.h
+TD_MODES = {"max_mean": 0, "max_max": 1, "double_mean": 2}
+TD_HEAD_WORKSPACE_BYTES, TD_HEAD_MAX_BATCH, ADAM_MAX_TENSORS, ADAM_CTL_BYTES = 4096, 1 << 20, 6, 32
+STAMPS_LIB_PATH =os.path.join(HERE, "libevg_stamps.so")  # `make -C csrc stamps`: in-kernel phase stamps (tools/stamps.py)
 
 NUM_PLAYERS, NUM_GROUPS, NUM_NODES, NUM_UNITS, NUM_ACTIONS, OBS_LEN = 2, 12, 11, 100, 7, 105
 MAX_SCORE = 3700
@@ -148,6 +154,25 @@ class EvgQnetGrads(C.Structure):
 class EvgMiniQnetGrads(C.Structure):
     """evg_mini_qnet_grads of include/evg_qnet_grad.h: where the Minimized network's parameter gradients go."""
     _fields_ = [("struct_size", C.c_uint32), ("reserved", C.c_uint32), ("w1", C.c_void_p), ("b1", C.c_void_p), ("w2", C.c_void_p), ("b2", C.c_void_p)]
+
+
+class EvgTdHeadArgs(C.Structure):
+    """evg_td_head_args of include/evg_learn.h: one sampled batch's operands and outputs (device pointers the caller owns)."""
+    _fields_ = [("struct_size", C.c_uint32), ("mode", C.c_int32), ("batch", C.c_int32), ("out", C.c_int32), ("scale", C.c_float),
+                ("reserved", C.c_uint32), ("q_pred", C.c_void_p), ("action", C.c_void_p), ("q_next", C.c_void_p), ("q_select", C.c_void_p),
+                ("reward", C.c_void_p), ("not_done", C.c_void_p), ("weights", C.c_void_p), ("gq", C.c_void_p), ("loss", C.c_void_p),
+                ("priorities", C.c_void_p), ("estimated", C.c_void_p), ("workspace", C.c_void_p), ("workspace_bytes", C.c_int64)]
+
+
+class EvgAdamTensor(C.Structure):
+    """evg_adam_tensor of include/evg_learn.h: one parameter tensor, its gradient and its two moments."""
+    _fields_ = [("param", C.c_void_p), ("grad", C.c_void_p), ("m", C.c_void_p), ("v", C.c_void_p), ("count", C.c_int64)]
+
+
+class EvgAdamArgs(C.Structure):
+    """evg_adam_args of include/evg_learn.h: one Adam step over the n tensors of one network."""
+    _fields_ = [("struct_size", C.c_uint32), ("n", C.c_int32), ("lr", C.c_float), ("beta1", C.c_float), ("beta2", C.c_float), ("eps", C.c_float),
+                ("clamp", C.c_float), ("fresh_state", C.c_int32), ("ctl", C.c_void_p), ("t", EvgAdamTensor * 6)]
 
 
 class EvgLeague(C.Structure):
@@ -285,6 +310,9 @@ def load(path=None):
     if hasattr(L, "evg_smart_qnet_backward"):        # libevg_grad.so only
         L.evg_smart_qnet_backward.argtypes = [vp, C.POINTER(EvgQnet), C.c_int64, vp, vp, C.POINTER(EvgQnetGrads), vp, C.c_int64, C.c_float, vp]
         L.evg_minimized_qnet_backward.argtypes = [vp, C.POINTER(EvgMiniQnet), C.c_int64, vp, vp, C.POINTER(EvgMiniQnetGrads), vp, C.c_int64, C.c_float, vp]
+    if hasattr(L, "evg_td_head"):                    # libevg_learn.so only
+        L.evg_td_head.argtypes = [vp, C.POINTER(EvgTdHeadArgs), vp]
+        L.evg_adam_step.argtypes = [vp, C.POINTER(EvgAdamArgs), vp]
     lp = C.POINTER(EvgLeague)
     L.evg_league_clear.argtypes = [vp, lp, vp]
     L.evg_league_assign.argtypes = [vp, lp, vp, vp]
@@ -371,6 +399,16 @@ def load_grad():
     missing = [n for n in GRAD_EXPORTS if not hasattr(L, n)]
     if missing:
         raise EvgError("%s does not export %s; rebuild it (make -C everglades-ai-wargame_amd/csrc grad)" % (GRAD_LIB_PATH, ", ".join(missing)))
+    return L
+
+
+def load_learn():
+    """Load libevg_learn.so: libevg.so's sources built with -DEVG_GRAD -DEVG_LEARN, which exports the entry points of include/evg.h plus GRAD_EXPORTS
+    plus LEARN_EXPORTS (include/evg_learn.h).  A handle of libevg.so is valid in it; a failed call's text is its own evg_last_error."""
+    L = load(LEARN_LIB_PATH)
+    missing = [n for n in GRAD_EXPORTS + LEARN_EXPORTS if not hasattr(L, n)]
+    if missing:
+        raise EvgError("%s does not export %s; rebuild it (make -C everglades-ai-wargame_amd/csrc learn)" % (LEARN_LIB_PATH, ", ".join(missing)))
     return L
 
 

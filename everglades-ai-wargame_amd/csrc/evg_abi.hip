@@ -1340,6 +1340,63 @@ int evg_minimized_qnet_backward(evg_handle* h, const evg_mini_qnet* net, int64_t
 } catch (...) { return on_exception(); }
 #endif
 
+#ifdef EVG_LEARN    // include/evg_learn.h; libevg_learn.so only
+static int learn_pointer(const char* what, const char* name, const void* p, bool required) {
+    if (!p) return required ? fail(EVG_ERR_INVALID, "%s: %s is NULL", what, name) : EVG_OK;
+    if (misaligned16(p)) return fail(EVG_ERR_INVALID, "%s: %s must be 16-byte aligned (got %p)", what, name, p);
+    return EVG_OK;
+}
+
+int evg_td_head(evg_handle* h, const evg_td_head_args* a, void* stream) try {
+    if (!h || !a) return fail(EVG_ERR_INVALID, "null handle or TD head descriptor");
+    if (a->struct_size != sizeof(evg_td_head_args))
+        return fail(EVG_ERR_INVALID, "td head: struct_size %u != sizeof(evg_td_head_args) %zu", a->struct_size, sizeof(evg_td_head_args));
+    if (a->batch < 1 || a->batch > EVG_TD_HEAD_MAX_BATCH) return fail(EVG_ERR_INVALID, "td head: batch must lie in 1..%d (got %d)", EVG_TD_HEAD_MAX_BATCH, a->batch);
+    if (a->out != 5 && a->out != 11) return fail(EVG_ERR_INVALID, "td head: out must be 5 or 11 (got %d)", a->out);
+    if (a->mode != EVG_TD_MAX_MEAN && a->mode != EVG_TD_MAX_MAX && a->mode != EVG_TD_DOUBLE_MEAN)
+        return fail(EVG_ERR_INVALID, "td head: unknown mode %d", a->mode);
+    if (!std::isfinite(a->scale)) return fail(EVG_ERR_INVALID, "td head: scale must be finite (got %g)", (double)a->scale);
+    const struct { const char* name; const void* p; bool required; } ptrs[] = {
+        {"q_pred", a->q_pred, true}, {"action", a->action, true}, {"q_next", a->q_next, true},
+        {"q_select", a->q_select, a->mode == EVG_TD_DOUBLE_MEAN}, {"reward", a->reward, true}, {"not_done", a->not_done, true},
+        {"weights", a->weights, false}, {"gq", a->gq, true}, {"loss", a->loss, true}, {"priorities", a->priorities, false},
+        {"estimated", a->estimated, false}, {"workspace", a->workspace, true}};
+    for (const auto& p : ptrs) {
+        const int rc = learn_pointer("td head", p.name, p.p, p.required);
+        if (rc) return rc;
+    }
+    if (a->workspace_bytes < EVG_TD_HEAD_WORKSPACE_BYTES)
+        return fail(EVG_ERR_INVALID, "td head: the workspace is too small (%lld bytes, need %lld)", (long long)a->workspace_bytes, (long long)EVG_TD_HEAD_WORKSPACE_BYTES);
+    EVG_ON_DEVICE(h);
+    return launched("td head", launch_td_head(*a, stream));
+} catch (...) { return on_exception(); }
+
+int evg_adam_step(evg_handle* h, const evg_adam_args* a, void* stream) try {
+    if (!h || !a) return fail(EVG_ERR_INVALID, "null handle or Adam descriptor");
+    if (a->struct_size != sizeof(evg_adam_args))
+        return fail(EVG_ERR_INVALID, "adam: struct_size %u != sizeof(evg_adam_args) %zu", a->struct_size, sizeof(evg_adam_args));
+    if (a->n < 1 || a->n > EVG_ADAM_MAX_TENSORS) return fail(EVG_ERR_INVALID, "adam: n must lie in 1..%d (got %d)", EVG_ADAM_MAX_TENSORS, a->n);
+    if (!std::isfinite(a->lr)) return fail(EVG_ERR_INVALID, "adam: lr must be finite (got %g)", (double)a->lr);
+    if (!(a->beta1 >= 0.0f && a->beta1 < 1.0f) || !(a->beta2 >= 0.0f && a->beta2 < 1.0f))
+        return fail(EVG_ERR_INVALID, "adam: the betas must lie in [0, 1) (got %g, %g)", (double)a->beta1, (double)a->beta2);
+    if (!(a->eps > 0.0f) || !std::isfinite(a->eps)) return fail(EVG_ERR_INVALID, "adam: eps must be finite and > 0 (got %g)", (double)a->eps);
+    if (!(a->clamp >= 0.0f) || !std::isfinite(a->clamp)) return fail(EVG_ERR_INVALID, "adam: clamp must be finite and >= 0 (got %g)", (double)a->clamp);
+    { const int rc = learn_pointer("adam", "ctl", a->ctl, true); if (rc) return rc; }
+    for (int i = 0; i < a->n; ++i) {
+        const evg_adam_tensor& t = a->t[i];
+        if (t.count < 1 || t.count > EVG_ADAM_MAX_COUNT)
+            return fail(EVG_ERR_INVALID, "adam: tensor %d: count must lie in 1..%d (got %lld)", i, EVG_ADAM_MAX_COUNT, (long long)t.count);
+        const struct { const char* name; const void* p; } ptrs[] = {{"param", t.param}, {"grad", t.grad}, {"m", t.m}, {"v", t.v}};
+        for (const auto& p : ptrs) {
+            if (!p.p) return fail(EVG_ERR_INVALID, "adam: tensor %d: %s is NULL", i, p.name);
+            if (misaligned16(p.p)) return fail(EVG_ERR_INVALID, "adam: tensor %d: %s must be 16-byte aligned (got %p)", i, p.name, p.p);
+        }
+    }
+    EVG_ON_DEVICE(h);
+    return launched("adam", launch_adam_step(*a, stream));
+} catch (...) { return on_exception(); }
+#endif
+
 // ---- self-royale (include/evg.h: evg_population_clear / _assign / _qnet) ----
 static int check_population(const evg_handle* h, const evg_population* pop, bool forward) {
     if (!h || !pop) return fail(EVG_ERR_INVALID, "null handle or population descriptor");

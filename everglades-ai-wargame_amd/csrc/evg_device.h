@@ -32,6 +32,9 @@
 #ifdef EVG_GRAD
 #include "../../include/evg_qnet_grad.h"
 #endif
+#ifdef EVG_LEARN
+#include "../../include/evg_learn.h"
+#endif
 #include "evg_rng.h"
 
 namespace evg {
@@ -277,6 +280,11 @@ int launch_smart_qnet_backward(const evg_qnet& net, long long rows, const float*
                                float clamp, int num_cu, void* stream);
 int launch_minimized_qnet_backward(const evg_mini_qnet& net, long long rows, const float* x, const float* gq, const evg_mini_qnet_grads& out,
                                    float* workspace, float clamp, int num_cu, void* stream);
+#endif
+#ifdef EVG_LEARN
+// the learner step's glue (learn_kernels.inc, libevg_learn.so); validated by the caller
+int launch_td_head(const evg_td_head_args& a, void* stream);
+int launch_adam_step(const evg_adam_args& a, void* stream);
 #endif
 // self-royale (population_kernels.inc); `pop` and the sizes are validated by the caller (evg_abi.hip)
 int launch_population_clear(const DevState& S, const evg_population& pop, void* stream);

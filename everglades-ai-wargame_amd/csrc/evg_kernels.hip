@@ -89,6 +89,9 @@ namespace evg {
 #ifdef EVG_GRAD                  // `make grad` (libevg_grad.so): the product's kernels plus ...
 #include "qnet_grad_kernels.inc"    // the backward pass of the two Q networks' expanded fp32 forward (optimize_model's policy forward)
 #endif
+#ifdef EVG_LEARN                 // `make learn` (libevg_learn.so, with EVG_GRAD): ... plus ...
+#include "learn_kernels.inc"        // the learner step's glue: the TD head (target, Huber loss, dLoss/dQ) and Adam over a network's tensors
+#endif
 
 // ---------------------------------------------------------------------------------------------
 // launchers

@@ -630,6 +630,19 @@ class EvergladesVecEnv(object):
         from . import qnet
         return qnet.make(self, net, final_relu, precision, qnet.SmartQNet, qnet.SmartQNetBf16)
 
+    def smart_learner(self, policy, target, mem, **kw):
+        """optimize_model for the Smart_State family on this env's device (everglades_amd.DqnLearner; include/evg_learn.h): `policy` and `target` as
+        smart_qnet() takes them (one network each), `mem` a smart_replay() or prioritized_replay().  Keywords: lr=1e-4, gamma=0.999, n_step=1,
+        mode="max_mean" | "max_max" | "double_mean", clamp=1.0, fresh_state=False, target_precision="fp32" | "bf16", betas=(0.9, 0.999), eps=1e-8,
+        beta=0.4 (the prioritized draw's), final_relu=None.  learner.step(batch_size, seed) is one training step without a torch op."""
+        from .learner import DqnLearner
+        return DqnLearner(self, "smart", policy, target, mem, **kw)
+
+    def minimized_learner(self, policy, target, mem, **kw):
+        """smart_learner() for the Minimized family (59-h-11 networks as minimized_qnet() takes them)."""
+        from .learner import DqnLearner
+        return DqnLearner(self, "minimized", policy, target, mem, **kw)
+
     @staticmethod
     def expand_smart_state(shared, swarm):
         """[N, 12, 59] from the compact pair (for checks; a consumer would rather split its first layer's weights)."""

@@ -12,7 +12,7 @@ forward inside optimize_model is torch's (its gradient is the loss's) or, with -
 forward with the device's backward pass behind it (include/evg_qnet_grad.h); the loss, the clamp and Adam are torch's either way.  A DQN loss need
 not decrease.
 
-    python examples/minimized_training.py [envs] [turns] [batch] [league] [--device-backward]
+    python examples/minimized_training.py [envs] [turns] [batch] [league] [--device-backward] [--device-learner]
 """
 import os
 import sys
@@ -52,7 +52,7 @@ def optimize_model(policy, target_eval, opt, batch, policy_forward=None):
 
 
 def main(num_envs=8192, turns=300, batch=256, opponent="random_actions", seat=0, seed=1, epsilon=0.3, league=False, acting_precision="fp32",
-         device_backward=False):
+         device_backward=False, device_learner=False):
     env = evg.EvergladesVecEnv(num_envs, seed=seed, auto_reset=True)
     policy, target = make_qnet(env.device, 0), make_qnet(env.device, 0)
     target.load_state_dict(policy.state_dict())
@@ -63,6 +63,9 @@ def main(num_envs=8192, turns=300, batch=256, opponent="random_actions", seat=0,
     target_eval = env.minimized_qnet(target, precision=acting_precision).expanded
     policy_forward = env.minimized_qnet(policy).with_grad if device_backward else None
     mem = env.smart_replay(8, n_step=N_STEP, gamma=GAMMA, shaping="custom", seats=seat)
+    # --device-learner: the whole optimize_model as env.minimized_learner's step (everglades_amd.DqnLearner, include/evg_learn.h): sample, the two
+    # forwards, the TD head, the backward pass and Adam are launches of the library; the learner owns the gradients and Adam's state
+    learner = env.minimized_learner(policy, target, mem, lr=LR, gamma=GAMMA, n_step=N_STEP, target_precision=acting_precision) if device_learner else None
     env.reset()
     if league:
         opponent = env.opponent_league(LEAGUE, seat=seat)
@@ -74,10 +77,12 @@ def main(num_envs=8192, turns=300, batch=256, opponent="random_actions", seat=0,
         q = act_net(*mem.slot_features(t))
         env.step_vs_q(opponent, q, epsilon, seat=seat, features=mem.slot_features(t + 1), actions_out=mem.slot_directions(t))
         mem.record(shaped=(env.reward[:, seat] / 10000.0).contiguous())
-        if t >= N_STEP + 1:
+        if t >= N_STEP + 1 and learner is not None:
+            losses.append(learner.step(batch, seed).clone())         # (the loss is the learner's own buffer: keep a copy for the report)
+        elif t >= N_STEP + 1:
             losses.append(optimize_model(policy, target_eval, opt, mem.sample(batch, seed=seed), policy_forward))
         if t % 100 == 99:
-            target.load_state_dict(policy.state_dict())
+            learner.sync_target() if learner is not None else target.load_state_dict(policy.state_dict())
             if league:
                 opponent.reweight()
     torch.cuda.synchronize()
@@ -87,14 +92,15 @@ def main(num_envs=8192, turns=300, batch=256, opponent="random_actions", seat=0,
     assert int(mem.size().item()) > 0
     print("%d envs x %d turns in %.3f s (%.1f M env-steps/s, network and learning included); memory holds %d transitions; loss first %.4g last %.4g, "
           "all finite: %s%s" % (num_envs, turns, dt, num_envs * turns / dt / 1e6, int(mem.size().item()), float(losses[0]), float(losses[-1]),
-                               bool(torch.isfinite(losses).all()), "; policy forward with the device backward" if device_backward else ""))
+                               bool(torch.isfinite(losses).all()), "; optimize_model on the device learner" if device_learner else
+                               "; policy forward with the device backward" if device_backward else ""))
     assert bool(torch.isfinite(losses).all())
     env.close()
     return losses
 
 
 if __name__ == "__main__":
-    a = [x for x in sys.argv[1:] if x != "--device-backward"]
+    a = [x for x in sys.argv[1:] if x not in ("--device-backward", "--device-learner")]
     precision = "fp32"                                    # --acting-precision {fp32,bf16}
     for i, x in enumerate(a):
         if x == "--acting-precision" or x.startswith("--acting-precision="):
@@ -104,4 +110,5 @@ if __name__ == "__main__":
     if precision not in ("fp32", "bf16"):
         sys.exit("--acting-precision must be fp32 or bf16")
     main(int(a[0]) if a else 8192, int(a[1]) if len(a) > 1 else 300, int(a[2]) if len(a) > 2 else 256, league=len(a) > 3 and a[3] in ("1", "league"),
-         acting_precision=precision, device_backward="--device-backward" in sys.argv[1:])
+         acting_precision=precision, device_backward="--device-backward" in sys.argv[1:],
+         device_learner="--device-learner" in sys.argv[1:])

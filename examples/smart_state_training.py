@@ -18,7 +18,11 @@ with the device's backward pass behind it (include/evg_qnet_grad.h).  The loss, 
 With --prioritized the memory is env.prioritized_replay (agents/DQN/PrioritizedMemory.py: alpha 0.6, beta 0.4): the batch is drawn by priority, the
 Huber loss is weighted per sample by the importance weights and |td| + 1e-5 goes back as the new priorities (evg_replay_update_priorities).
 
-    python examples/smart_state_training.py [envs] [turns] [batch] [device_net] [--prioritized] [--device-backward]
+With --device-learner the whole of optimize_model is env.smart_learner's step (everglades_amd.DqnLearner, include/evg_learn.h): sample, the two
+forwards, the TD head, the backward pass and Adam are launches of the library and no torch op runs between the memory and the updated parameters.  It
+implies the device networks and combines with --prioritized and --acting-precision (the target network's precision).
+
+    python examples/smart_state_training.py [envs] [turns] [batch] [device_net] [--prioritized] [--device-backward] [--device-learner]
 """
 import os
 import sys
@@ -69,14 +73,14 @@ def optimize_model(policy, target, opt, batch, target_eval=None, weights=None, p
 
 
 def main(num_envs=8192, turns=300, batch=1024, opponent="swarm_agent", seat=0, seed=1, epsilon=0.3, device_net=False, prioritized=False,
-         acting_precision="fp32", device_backward=False):
+         acting_precision="fp32", device_backward=False, device_learner=False):
     env = evg.EvergladesVecEnv(num_envs, seed=seed, auto_reset=True)
     dev = env.device
     policy, target = make_qnet(dev, 0), make_qnet(dev, 0)
     target.load_state_dict(policy.state_dict())
     opt = torch.optim.Adam(policy.parameters(), lr=LR)
     act_net = target_eval = None
-    if device_net or acting_precision != "fp32":
+    if device_net or device_learner or acting_precision != "fp32":
         # acting and the target network on the device; "bf16": both on the bf16 matrix cores (include/evg_qnet_bf16.h).  The policy forward whose
         # gradient the loss needs is torch's, or (device_backward) the fp32 evaluator's with_grad: the gradient is defined on the fp32 chain.
         act_net = env.smart_qnet(policy, precision=acting_precision)
@@ -86,6 +90,8 @@ def main(num_envs=8192, turns=300, batch=1024, opponent="swarm_agent", seat=0, s
         mem = env.prioritized_replay(8, alpha=0.6, n_step=N_STEP, gamma=GAMMA, shaping="reward_short_games", seats=seat)
     else:
         mem = env.smart_replay(8, n_step=N_STEP, gamma=GAMMA, shaping="reward_short_games", seats=seat)
+    # the whole optimize_model on the device: the learner owns the gradients and Adam's state, `opt` stays unused
+    learner = env.smart_learner(policy, target, mem, lr=LR, gamma=GAMMA, n_step=N_STEP, target_precision=acting_precision) if device_learner else None
     env.reset()
     env.smart_state_compact(-1, env.observe_seat(seat), *mem.slot_features(0))   # record 0's features
     losses = []
@@ -96,14 +102,18 @@ def main(num_envs=8192, turns=300, batch=1024, opponent="swarm_agent", seat=0, s
             q = q_values(policy, *mem.slot_features(t)) if act_net is None else act_net(*mem.slot_features(t))
         env.step_vs_q(opponent, q, epsilon, seat=seat, features=mem.slot_features(t + 1), directions=mem.slot_directions(t))
         mem.record()
-        if t >= N_STEP + 1 and prioritized:
+        if t >= N_STEP + 1 and learner is not None:
+            losses.append(learner.step(batch, seed).clone())         # (the loss is the learner's own buffer: keep a copy for the report)
+        elif t >= N_STEP + 1 and prioritized:
             out = mem.sample(batch, seed=seed, beta=0.4)
             loss, priorities = optimize_model(policy, target, opt, out[:5], target_eval, weights=out[5], policy_forward=policy_forward)
             mem.update_priorities(out[6], priorities)
             losses.append(loss)
         elif t >= N_STEP + 1:
             losses.append(optimize_model(policy, target, opt, mem.sample(batch, seed=seed), target_eval, policy_forward=policy_forward))
-        if t % 100 == 99:
+        if t % 100 == 99 and learner is not None:
+            learner.sync_target()
+        elif t % 100 == 99:
             target.load_state_dict(policy.state_dict())
     torch.cuda.synchronize()
     dt = time.perf_counter() - t0
@@ -111,14 +121,15 @@ def main(num_envs=8192, turns=300, batch=1024, opponent="swarm_agent", seat=0, s
     mem.check()
     print("%d envs x %d turns in %.3f s (%.1f M env-steps/s, network and learning included); memory holds %d transitions; loss first %.4g last %.4g, "
           "all finite: %s%s" % (num_envs, turns, dt, num_envs * turns / dt / 1e6, int(mem.size().item()), float(losses[0]), float(losses[-1]),
-                               bool(torch.isfinite(losses).all()), "; policy forward with the device backward" if device_backward else ""))
+                               bool(torch.isfinite(losses).all()), "; optimize_model on the device learner" if device_learner else
+                               "; policy forward with the device backward" if device_backward else ""))
     assert bool(torch.isfinite(losses).all())
     env.close()
     return losses
 
 
 if __name__ == "__main__":
-    a = [x for x in sys.argv[1:] if x not in ("--prioritized", "--device-backward")]
+    a = [x for x in sys.argv[1:] if x not in ("--prioritized", "--device-backward", "--device-learner")]
     precision = "fp32"                                    # --acting-precision {fp32,bf16} (implies the device network for bf16)
     for i, x in enumerate(a):
         if x == "--acting-precision" or x.startswith("--acting-precision="):
@@ -128,4 +139,5 @@ if __name__ == "__main__":
     if precision not in ("fp32", "bf16"):
         sys.exit("--acting-precision must be fp32 or bf16")
     main(int(a[0]) if a else 8192, int(a[1]) if len(a) > 1 else 300, int(a[2]) if len(a) > 2 else 1024, device_net=len(a) > 3 and a[3] in ("1", "device_net"),
-         prioritized="--prioritized" in sys.argv[1:], acting_precision=precision, device_backward="--device-backward" in sys.argv[1:])
+         prioritized="--prioritized" in sys.argv[1:], acting_precision=precision, device_backward="--device-backward" in sys.argv[1:],
+         device_learner="--device-learner" in sys.argv[1:])
