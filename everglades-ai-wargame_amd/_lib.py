@@ -28,6 +28,12 @@ LEARN_EXPORTS = ["evg_td_head", "evg_adam_step"]
 # EVG_TD_* modes, EVG_TD_HEAD_WORKSPACE_BYTES, EVG_TD_HEAD_MAX_BATCH, EVG_ADAM_MAX_TENSORS, EVG_ADAM_CTL_BYTES of include/evg_learn.h
 TD_MODES = {"max_mean": 0, "max_max": 1, "double_mean": 2}
 TD_HEAD_WORKSPACE_BYTES, TD_HEAD_MAX_BATCH, ADAM_MAX_TENSORS, ADAM_CTL_BYTES = 4096, 1 << 20, 6, 32
+# `make -C csrc poplearn`: ... plus the six entry points of include/evg_pop_learn.h (PopulationLearner loads it: load_poplearn)
+POPLEARN_LIB_PATH = os.path.join(HERE, "libevg_poplearn.so")
+POPLEARN_EXPORTS = ["evg_pop_learn_expand_ids", "evg_pop_learn_take_rows", "evg_td_head_grouped", "evg_smart_population_backward", "evg_population_backward",
+                    "evg_adam_step_grouped"]
+# EVG_POP_LEARN_MAX_PARTIALS, EVG_TD_HEAD_GROUPED_WORKSPACE_BYTES, EVG_POP_LEARN_MAX_TENSORS of include/evg_pop_learn.h
+POP_LEARN_MAX_PARTIALS, TD_HEAD_GROUPED_WORKSPACE_BYTES, POP_LEARN_MAX_TENSORS = 512 + 16, 4 * 1024 * 16, 6
 STAMPS_LIB_PATH =os.path.join(HERE, "libevg_stamps.so")  # `make -C csrc stamps`: in-kernel phase stamps (tools/stamps.py)
 
 NUM_PLAYERS, NUM_GROUPS, NUM_NODES, NUM_UNITS, NUM_ACTIONS, OBS_LEN = 2, 12, 11, 100, 7, 105
@@ -175,6 +181,31 @@ class EvgAdamArgs(C.Structure):
                 ("clamp", C.c_float), ("fresh_state", C.c_int32), ("ctl", C.c_void_p), ("t", EvgAdamTensor * 6)]
 
 
+class EvgPopLists(C.Structure):
+    """evg_pop_lists of include/evg_pop_learn.h: the bucket pass's results that name each member's rows."""
+    _fields_ = [("index", C.c_void_p), ("first", C.c_void_p), ("count", C.c_void_p), ("num_members", C.c_int32), ("batch", C.c_int32)]
+
+
+class EvgTdHeadGroupedArgs(C.Structure):
+    """evg_td_head_grouped_args of include/evg_pop_learn.h: evg_td_head's operands and the lists."""
+    _fields_ = [("struct_size", C.c_uint32), ("reserved", C.c_uint32), ("td", EvgTdHeadArgs), ("lists", EvgPopLists)]
+
+
+class EvgPopBackwardArgs(C.Structure):
+    """evg_pop_backward_args of include/evg_pop_learn.h: the members' parameters [tensor][member] and where their gradients go."""
+    _fields_ = [("struct_size", C.c_uint32), ("h1", C.c_int32), ("h2", C.c_int32), ("final_relu", C.c_int32), ("clamp", C.c_float),
+                ("reserved", C.c_uint32), ("lists", EvgPopLists), ("x", C.c_void_p), ("gq", C.c_void_p), ("param", (C.c_void_p * 16) * 6),
+                ("grad", (C.c_void_p * 16) * 6), ("workspace", C.c_void_p), ("workspace_bytes", C.c_int64)]
+
+
+class EvgAdamGroupedArgs(C.Structure):
+    """evg_adam_grouped_args of include/evg_pop_learn.h: one Adam step per member over its n tensors, [tensor][member]."""
+    _fields_ = [("struct_size", C.c_uint32), ("n", C.c_int32), ("lr", C.c_float), ("beta1", C.c_float), ("beta2", C.c_float), ("eps", C.c_float),
+                ("clamp", C.c_float), ("fresh_state", C.c_int32), ("num_members", C.c_int32), ("reserved", C.c_uint32), ("count", C.c_void_p),
+                ("ctl", C.c_void_p), ("elements", C.c_int64 * 6), ("param", (C.c_void_p * 16) * 6), ("grad", (C.c_void_p * 16) * 6),
+                ("m", (C.c_void_p * 16) * 6), ("v", (C.c_void_p * 16) * 6)]
+
+
 class EvgLeague(C.Structure):
     """evg_league of include/evg.h: the descriptor of an opponent league (device pointers the caller owns)."""
     _fields_ = [
@@ -313,6 +344,13 @@ def load(path=None):
     if hasattr(L, "evg_td_head"):                    # libevg_learn.so only
         L.evg_td_head.argtypes = [vp, C.POINTER(EvgTdHeadArgs), vp]
         L.evg_adam_step.argtypes = [vp, C.POINTER(EvgAdamArgs), vp]
+    if hasattr(L, "evg_td_head_grouped"):            # libevg_poplearn.so only
+        L.evg_pop_learn_expand_ids.argtypes = [vp, vp, C.c_int32, C.c_int32, vp, vp]
+        L.evg_pop_learn_take_rows.argtypes = [vp, vp, vp, C.c_int32, C.c_int32, C.c_int64, C.c_int32, vp, vp]
+        L.evg_td_head_grouped.argtypes = [vp, C.POINTER(EvgTdHeadGroupedArgs), vp]
+        L.evg_smart_population_backward.argtypes = [vp, C.POINTER(EvgPopBackwardArgs), vp]
+        L.evg_population_backward.argtypes = [vp, C.POINTER(EvgPopBackwardArgs), vp]
+        L.evg_adam_step_grouped.argtypes = [vp, C.POINTER(EvgAdamGroupedArgs), vp]
     lp = C.POINTER(EvgLeague)
     L.evg_league_clear.argtypes = [vp, lp, vp]
     L.evg_league_assign.argtypes = [vp, lp, vp, vp]
@@ -409,6 +447,16 @@ def load_learn():
     missing = [n for n in GRAD_EXPORTS + LEARN_EXPORTS if not hasattr(L, n)]
     if missing:
         raise EvgError("%s does not export %s; rebuild it (make -C everglades-ai-wargame_amd/csrc learn)" % (LEARN_LIB_PATH, ", ".join(missing)))
+    return L
+
+
+def load_poplearn():
+    """Load libevg_poplearn.so: libevg.so's sources built with -DEVG_GRAD -DEVG_LEARN -DEVG_POP_LEARN, which exports what libevg_learn.so does plus
+    POPLEARN_EXPORTS (include/evg_pop_learn.h).  A handle of libevg.so is valid in it; a failed call's text is its own evg_last_error."""
+    L = load(POPLEARN_LIB_PATH)
+    missing = [n for n in GRAD_EXPORTS + LEARN_EXPORTS + POPLEARN_EXPORTS if not hasattr(L, n)]
+    if missing:
+        raise EvgError("%s does not export %s; rebuild it (make -C everglades-ai-wargame_amd/csrc poplearn)" % (POPLEARN_LIB_PATH, ", ".join(missing)))
     return L
 
 

@@ -1397,6 +1397,135 @@ int evg_adam_step(evg_handle* h, const evg_adam_args* a, void* stream) try {
 } catch (...) { return on_exception(); }
 #endif
 
+#ifdef EVG_POP_LEARN    // include/evg_pop_learn.h; libevg_poplearn.so only
+static int pop_lists_check(const char* what, const evg_pop_lists& l) {
+    if (l.num_members < 1 || l.num_members > EVG_POP_MAX_MEMBERS)
+        return fail(EVG_ERR_INVALID, "%s: num_members must lie in 1..%d (got %d)", what, EVG_POP_MAX_MEMBERS, l.num_members);
+    if (l.batch < 1 || l.batch > EVG_TD_HEAD_MAX_BATCH) return fail(EVG_ERR_INVALID, "%s: batch must lie in 1..%d (got %d)", what, EVG_TD_HEAD_MAX_BATCH, l.batch);
+    const struct { const char* name; const void* p; } ptrs[] = {{"lists.index", l.index}, {"lists.first", l.first}, {"lists.count", l.count}};
+    for (const auto& p : ptrs) {
+        if (!p.p) return fail(EVG_ERR_INVALID, "%s: %s is NULL", what, p.name);
+        if (reinterpret_cast<uintptr_t>(p.p) % 4) return fail(EVG_ERR_INVALID, "%s: %s must be 4-byte aligned (got %p)", what, p.name, p.p);
+    }
+    return EVG_OK;
+}
+
+int evg_pop_learn_expand_ids(evg_handle* h, const uint8_t* member, int32_t batch, int32_t repeat, uint8_t* out, void* stream) try {
+    if (!h || !member || !out) return fail(EVG_ERR_INVALID, "expand ids: null handle, member or out");
+    if (batch < 1 || batch > EVG_TD_HEAD_MAX_BATCH) return fail(EVG_ERR_INVALID, "expand ids: batch must lie in 1..%d (got %d)", EVG_TD_HEAD_MAX_BATCH, batch);
+    if (repeat < 1 || repeat > 64) return fail(EVG_ERR_INVALID, "expand ids: repeat must lie in 1..64 (got %d)", repeat);
+    EVG_ON_DEVICE(h);
+    return launched("expand ids", launch_pop_expand_ids(member, batch, repeat, out, stream));
+} catch (...) { return on_exception(); }
+
+int evg_pop_learn_take_rows(evg_handle* h, const float* src, const uint8_t* ids, int32_t member, int32_t num_members, int64_t rows, int32_t width,
+                            float* dst, void* stream) try {
+    if (!h || !src || !ids || !dst) return fail(EVG_ERR_INVALID, "take rows: null handle, src, ids or dst");
+    if (num_members < 1 || num_members > EVG_POP_MAX_MEMBERS)
+        return fail(EVG_ERR_INVALID, "take rows: num_members must lie in 1..%d (got %d)", EVG_POP_MAX_MEMBERS, num_members);
+    if (member < 0 || member >= num_members) return fail(EVG_ERR_INVALID, "take rows: member must lie in 0..%d (got %d)", num_members - 1, member);
+    if (rows < 1 || rows > 64LL * EVG_TD_HEAD_MAX_BATCH)
+        return fail(EVG_ERR_INVALID, "take rows: rows must lie in 1..%lld (got %lld)", 64LL * EVG_TD_HEAD_MAX_BATCH, (long long)rows);
+    if (width < 1 || width > 16) return fail(EVG_ERR_INVALID, "take rows: width must lie in 1..16 (got %d)", width);
+    if (reinterpret_cast<uintptr_t>(src) % 4 || reinterpret_cast<uintptr_t>(dst) % 4)
+        return fail(EVG_ERR_INVALID, "take rows: src and dst must be 4-byte aligned (got %p, %p)", (const void*)src, (void*)dst);
+    EVG_ON_DEVICE(h);
+    return launched("take rows", launch_pop_take_rows(src, ids, member, num_members, (long long)rows, width, dst, stream));
+} catch (...) { return on_exception(); }
+
+int evg_td_head_grouped(evg_handle* h, const evg_td_head_grouped_args* g, void* stream) try {
+    if (!h || !g) return fail(EVG_ERR_INVALID, "null handle or grouped TD head descriptor");
+    if (g->struct_size != sizeof(evg_td_head_grouped_args))
+        return fail(EVG_ERR_INVALID, "grouped td head: struct_size %u != sizeof(evg_td_head_grouped_args) %zu", g->struct_size, sizeof(evg_td_head_grouped_args));
+    const evg_td_head_args* a = &g->td;
+    if (a->struct_size != sizeof(evg_td_head_args))
+        return fail(EVG_ERR_INVALID, "grouped td head: td.struct_size %u != sizeof(evg_td_head_args) %zu", a->struct_size, sizeof(evg_td_head_args));
+    { const int rc = pop_lists_check("grouped td head", g->lists); if (rc) return rc; }
+    if (a->batch != g->lists.batch) return fail(EVG_ERR_INVALID, "grouped td head: td.batch %d != lists.batch %d", a->batch, g->lists.batch);
+    if (a->out != 5 && a->out != 11) return fail(EVG_ERR_INVALID, "grouped td head: out must be 5 or 11 (got %d)", a->out);
+    if (a->mode != EVG_TD_MAX_MEAN && a->mode != EVG_TD_MAX_MAX && a->mode != EVG_TD_DOUBLE_MEAN)
+        return fail(EVG_ERR_INVALID, "grouped td head: unknown mode %d", a->mode);
+    if (!std::isfinite(a->scale)) return fail(EVG_ERR_INVALID, "grouped td head: scale must be finite (got %g)", (double)a->scale);
+    const struct { const char* name; const void* p; bool required; } ptrs[] = {
+        {"q_pred", a->q_pred, true}, {"action", a->action, true}, {"q_next", a->q_next, true},
+        {"q_select", a->q_select, a->mode == EVG_TD_DOUBLE_MEAN}, {"reward", a->reward, true}, {"not_done", a->not_done, true},
+        {"weights", a->weights, false}, {"gq", a->gq, true}, {"loss", a->loss, true}, {"priorities", a->priorities, false},
+        {"estimated", a->estimated, false}, {"workspace", a->workspace, true}};
+    for (const auto& p : ptrs) {
+        const int rc = learn_pointer("grouped td head", p.name, p.p, p.required);
+        if (rc) return rc;
+    }
+    if (a->workspace_bytes < EVG_TD_HEAD_GROUPED_WORKSPACE_BYTES)
+        return fail(EVG_ERR_INVALID, "grouped td head: the workspace is too small (%lld bytes, need %lld)", (long long)a->workspace_bytes,
+                    (long long)EVG_TD_HEAD_GROUPED_WORKSPACE_BYTES);
+    EVG_ON_DEVICE(h);
+    return launched("grouped td head", launch_td_head_grouped(*g, stream));
+} catch (...) { return on_exception(); }
+
+static int pop_backward_call(evg_handle* h, const evg_pop_backward_args* a, void* stream, int tensors, int max_hidden, int64_t partial_floats,
+                             int (*launch)(const evg_pop_backward_args&, int, void*)) {
+    if (!h || !a) return fail(EVG_ERR_INVALID, "null handle or population backward descriptor");
+    if (a->struct_size != sizeof(evg_pop_backward_args))
+        return fail(EVG_ERR_INVALID, "population backward: struct_size %u != sizeof(evg_pop_backward_args) %zu", a->struct_size, sizeof(evg_pop_backward_args));
+    { const int rc = pop_lists_check("population backward", a->lists); if (rc) return rc; }
+    if (a->h1 < 1 || a->h1 > max_hidden || (tensors == 6 && (a->h2 < 1 || a->h2 > max_hidden)))
+        return fail(EVG_ERR_INVALID, "population backward: the hidden sizes must lie in 1..%d (got %d, %d)", max_hidden, a->h1, a->h2);
+    if (!(a->clamp >= 0.0f) || !std::isfinite(a->clamp)) return fail(EVG_ERR_INVALID, "population backward: clamp must be finite and >= 0 (got %g)", (double)a->clamp);
+    { const int rc = learn_pointer("population backward", "x", a->x, true); if (rc) return rc; }
+    { const int rc = learn_pointer("population backward", "gq", a->gq, true); if (rc) return rc; }
+    { const int rc = learn_pointer("population backward", "workspace", a->workspace, true); if (rc) return rc; }
+    for (int i = 0; i < tensors; ++i)
+        for (int m = 0; m < a->lists.num_members; ++m) {
+            if (!a->param[i][m] || !a->grad[i][m]) return fail(EVG_ERR_INVALID, "population backward: tensor %d of member %d is NULL", i, m);
+            if (misaligned16(a->param[i][m]) || misaligned16(a->grad[i][m]))
+                return fail(EVG_ERR_INVALID, "population backward: tensor %d of member %d must be 16-byte aligned", i, m);
+        }
+    const int64_t need = 4 * partial_floats * ((int64_t)qnet_grad_blocks((long long)a->lists.batch, h->caps.cus) + a->lists.num_members);
+    if (a->workspace_bytes < need)
+        return fail(EVG_ERR_INVALID, "population backward: the workspace is too small (%lld bytes, %d rows of %d members need %lld)",
+                    (long long)a->workspace_bytes, a->lists.batch, a->lists.num_members, (long long)need);
+    EVG_ON_DEVICE(h);
+    return launched("population backward", launch(*a, h->caps.cus, stream));
+}
+
+int evg_smart_population_backward(evg_handle* h, const evg_pop_backward_args* a, void* stream) try {
+    return pop_backward_call(h, a, stream, 6, EVG_QNET_MAX_HIDDEN, EVG_SMART_QNET_GRAD_PARTIAL, launch_smart_population_backward);
+} catch (...) { return on_exception(); }
+
+int evg_population_backward(evg_handle* h, const evg_pop_backward_args* a, void* stream) try {
+    return pop_backward_call(h, a, stream, 4, EVG_MINI_QNET_MAX_HIDDEN, EVG_MINI_QNET_GRAD_PARTIAL, launch_population_backward);
+} catch (...) { return on_exception(); }
+
+int evg_adam_step_grouped(evg_handle* h, const evg_adam_grouped_args* a, void* stream) try {
+    if (!h || !a) return fail(EVG_ERR_INVALID, "null handle or grouped Adam descriptor");
+    if (a->struct_size != sizeof(evg_adam_grouped_args))
+        return fail(EVG_ERR_INVALID, "grouped adam: struct_size %u != sizeof(evg_adam_grouped_args) %zu", a->struct_size, sizeof(evg_adam_grouped_args));
+    if (a->n < 1 || a->n > EVG_POP_LEARN_MAX_TENSORS) return fail(EVG_ERR_INVALID, "grouped adam: n must lie in 1..%d (got %d)", EVG_POP_LEARN_MAX_TENSORS, a->n);
+    if (a->num_members < 1 || a->num_members > EVG_POP_MAX_MEMBERS)
+        return fail(EVG_ERR_INVALID, "grouped adam: num_members must lie in 1..%d (got %d)", EVG_POP_MAX_MEMBERS, a->num_members);
+    if (!std::isfinite(a->lr)) return fail(EVG_ERR_INVALID, "grouped adam: lr must be finite (got %g)", (double)a->lr);
+    if (!(a->beta1 >= 0.0f && a->beta1 < 1.0f) || !(a->beta2 >= 0.0f && a->beta2 < 1.0f))
+        return fail(EVG_ERR_INVALID, "grouped adam: the betas must lie in [0, 1) (got %g, %g)", (double)a->beta1, (double)a->beta2);
+    if (!(a->eps > 0.0f) || !std::isfinite(a->eps)) return fail(EVG_ERR_INVALID, "grouped adam: eps must be finite and > 0 (got %g)", (double)a->eps);
+    if (!(a->clamp >= 0.0f) || !std::isfinite(a->clamp)) return fail(EVG_ERR_INVALID, "grouped adam: clamp must be finite and >= 0 (got %g)", (double)a->clamp);
+    { const int rc = learn_pointer("grouped adam", "ctl", a->ctl, true); if (rc) return rc; }
+    if (!a->count || reinterpret_cast<uintptr_t>(a->count) % 4) return fail(EVG_ERR_INVALID, "grouped adam: count is NULL or not 4-byte aligned");
+    for (int i = 0; i < a->n; ++i) {
+        if (a->elements[i] < 1 || a->elements[i] > EVG_ADAM_MAX_COUNT)
+            return fail(EVG_ERR_INVALID, "grouped adam: tensor %d: elements must lie in 1..%d (got %lld)", i, EVG_ADAM_MAX_COUNT, (long long)a->elements[i]);
+        for (int m = 0; m < a->num_members; ++m) {
+            const void* const ptrs[4] = {a->param[i][m], a->grad[i][m], a->m[i][m], a->v[i][m]};
+            for (const void* p : ptrs) {
+                if (!p) return fail(EVG_ERR_INVALID, "grouped adam: a pointer of tensor %d of member %d is NULL", i, m);
+                if (misaligned16(p)) return fail(EVG_ERR_INVALID, "grouped adam: the pointers of tensor %d of member %d must be 16-byte aligned (got %p)", i, m, p);
+            }
+        }
+    }
+    EVG_ON_DEVICE(h);
+    return launched("grouped adam", launch_adam_step_grouped(*a, stream));
+} catch (...) { return on_exception(); }
+#endif
+
 // ---- self-royale (include/evg.h: evg_population_clear / _assign / _qnet) ----
 static int check_population(const evg_handle* h, const evg_population* pop, bool forward) {
     if (!h || !pop) return fail(EVG_ERR_INVALID, "null handle or population descriptor");

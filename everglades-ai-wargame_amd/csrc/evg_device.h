@@ -35,6 +35,9 @@
 #ifdef EVG_LEARN
 #include "../../include/evg_learn.h"
 #endif
+#ifdef EVG_POP_LEARN
+#include "../../include/evg_pop_learn.h"
+#endif
 #include "evg_rng.h"
 
 namespace evg {
@@ -285,6 +288,15 @@ int launch_minimized_qnet_backward(const evg_mini_qnet& net, long long rows, con
 // the learner step's glue (learn_kernels.inc, libevg_learn.so); validated by the caller
 int launch_td_head(const evg_td_head_args& a, void* stream);
 int launch_adam_step(const evg_adam_args& a, void* stream);
+#endif
+#ifdef EVG_POP_LEARN
+// the grouped learner step of a population (pop_learn_kernels.inc, libevg_poplearn.so); validated by the caller
+int launch_pop_expand_ids(const uint8_t* member, int batch, int repeat, uint8_t* out, void* stream);
+int launch_pop_take_rows(const float* src, const uint8_t* ids, int member, int num, long long rows, int width, float* dst, void* stream);
+int launch_td_head_grouped(const evg_td_head_grouped_args& a, void* stream);
+int launch_smart_population_backward(const evg_pop_backward_args& a, int num_cu, void* stream);
+int launch_population_backward(const evg_pop_backward_args& a, int num_cu, void* stream);
+int launch_adam_step_grouped(const evg_adam_grouped_args& a, void* stream);
 #endif
 // self-royale (population_kernels.inc); `pop` and the sizes are validated by the caller (evg_abi.hip)
 int launch_population_clear(const DevState& S, const evg_population& pop, void* stream);

@@ -92,6 +92,9 @@ namespace evg {
 #ifdef EVG_LEARN                 // `make learn` (libevg_learn.so, with EVG_GRAD): ... plus ...
 #include "learn_kernels.inc"        // the learner step's glue: the TD head (target, Huber loss, dLoss/dQ) and Adam over a network's tensors
 #endif
+#ifdef EVG_POP_LEARN             // `make poplearn` (libevg_poplearn.so, with EVG_GRAD and EVG_LEARN): ... plus ...
+#include "pop_learn_kernels.inc"    // self-royale: the grouped TD head, backward and Adam that train every member of a team from one batch
+#endif
 
 // ---------------------------------------------------------------------------------------------
 // launchers

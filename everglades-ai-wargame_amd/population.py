@@ -89,6 +89,20 @@ class QPopulation(object):
             self._hist = torch.zeros((2, _lib.POP_BINS, (rows + _lib.POP_BLOCK - 1) // _lib.POP_BLOCK), dtype=torch.int32, device=self.env.device)
         self._desc.index, self._desc.hist, self._desc.scratch_rows = self._index.data_ptr(), self._hist.data_ptr(), rows
 
+    def reserve(self, rows):
+        """scratch for forwards of up to `rows` rows.  -> the scratch tensors it replaced (a graph captured before the call still reads them: keep them
+        while it lives), or None where the scratch was large enough"""
+        if rows <= self._desc.scratch_rows:
+            return None
+        old = (self._index, self._hist)
+        self._scratch(rows)
+        return old
+
+    def lists(self):
+        """the bucket pass's results of the last forward for seat slot 0 (what expanded() uses): (index, first [17], count [17]), int32 views; member
+        m's rows, ascending, are index[first[m] : first[m] + count[m]], bin 16 the rows of nobody.  `index` is replaced when the scratch grows."""
+        return self._index, self._bins[0, 0], self._bins[1, 0]
+
     def _descriptor(self, rows):
         if not 1 <= rows <= _lib.POP_MAX_ROWS:
             raise ValueError("rows must lie in 1..2^24 (got %d)" % rows)

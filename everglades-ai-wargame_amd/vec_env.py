@@ -643,6 +643,19 @@ class EvergladesVecEnv(object):
         from .learner import DqnLearner
         return DqnLearner(self, "minimized", policy, target, mem, **kw)
 
+    def smart_population_learner(self, policies, targets, **kw):
+        """Self-royale's optimize_model for one team of Smart_State networks on this env's device (everglades_amd.PopulationLearner;
+        include/evg_pop_learn.h): `policies` and `targets` are lists of K networks (1..16) as smart_qnet() takes them, one (h1, h2) and one final_relu.
+        Keywords: smart_learner()'s without `beta`.  learner.step_on(batch, member) trains every member on the rows it played (member uint8 [B]; an id
+        >= K is nobody of this team) in one chain of launches without a torch op.  Create it after env.reset()."""
+        from .pop_learner import PopulationLearner
+        return PopulationLearner(self, "smart", policies, targets, **kw)
+
+    def minimized_population_learner(self, policies, targets, **kw):
+        """smart_population_learner() for the Minimized family (59-h-11 networks as minimized_qnet() takes them)."""
+        from .pop_learner import PopulationLearner
+        return PopulationLearner(self, "minimized", policies, targets, **kw)
+
     @staticmethod
     def expand_smart_state(shared, swarm):
         """[N, 12, 59] from the compact pair (for checks; a consumer would rather split its first layer's weights)."""

@@ -14,7 +14,11 @@ Where this departs from the script: one batch is drawn for all eight learners an
 that played; a member with no transition in the batch takes a zero loss and no step.  `played` holds the members of every turn (a copy of pop.member ahead
 of the step: end_of_turn's history= names the members of the envs whose episode ended, here kept as last_game).  A DQN loss need not decrease.
 
-    python examples/smart_state_self_royale.py [envs] [turns] [batch]
+    python examples/smart_state_self_royale.py [envs] [turns] [batch] [--device-learner]
+
+--device-learner: the learning block is two PopulationLearners (everglades_amd.PopulationLearner, one per seat's team): one step_on per seat trains
+every member on the rows it played, with the other seat's rows passed as id 255 -- no torch forward, backward or optimizer.  There a member without
+a row in the batch really takes no step (the torch loop's zero-gradient opt.step() still moves its parameters through Adam's moments).
 """
 import os
 import sys
@@ -30,18 +34,23 @@ from smart_state_training import GAMMA, LR, N_STEP, make_qnet
 NUM_AGENTS_PER_TEAM = 4
 
 
-def main(num_envs=8192, turns=300, batch=256, seed=1, team_size=NUM_AGENTS_PER_TEAM):
+def main(num_envs=8192, turns=300, batch=256, seed=1, team_size=NUM_AGENTS_PER_TEAM, device_learner=False):
     env = evg.EvergladesVecEnv(num_envs, seed=seed, auto_reset=True)
     dev, K = env.device, team_size
     policies = [[make_qnet(dev, 10 * p + m) for m in range(K)] for p in range(2)]
     targets = [[make_qnet(dev, 10 * p + m) for m in range(K)] for p in range(2)]
-    opts = [[torch.optim.Adam(policies[p][m].parameters(), lr=LR) for m in range(K)] for p in range(2)]
     # each member explores at its own rate: epsilon [N, 2] is gathered from this table by the members that play
     eps_table = torch.stack([torch.linspace(0.1, 0.4, K), torch.linspace(0.4, 0.1, K)]).to(dev)
     mem = env.smart_replay(8, n_step=N_STEP, gamma=GAMMA, shaping="custom", seats=(0, 1))
     obs = env.reset()
     pop = env.smart_q_population(policies[0], policies[1])                                     # the acting networks, drawn per env and episode
-    tpop = env.smart_q_population(targets[0], targets[1], max_rows=12 * batch)                 # the target networks, evaluated by recorded member
+    if device_learner:                                                                     # one learner per seat's team; it owns the target forward
+        learners = [env.smart_population_learner(policies[p], targets[p], lr=LR, gamma=GAMMA, n_step=N_STEP, mode="max_mean", clamp=1.0)
+                    for p in range(2)]
+        nobody = torch.full((batch,), 255, dtype=torch.uint8, device=dev)
+    else:
+        opts = [[torch.optim.Adam(policies[p][m].parameters(), lr=LR) for m in range(K)] for p in range(2)]
+        tpop = env.smart_q_population(targets[0], targets[1], max_rows=12 * batch)                 # the target networks, evaluated by recorded member
     shared0, swarm0 = mem.slot_features(0)
     for p in range(2):                                                                     # the first features; afterwards the step launch writes them
         s, w = env.smart_state_compact(p, obs)
@@ -67,22 +76,27 @@ def main(num_envs=8192, turns=300, batch=256, seed=1, team_size=NUM_AGENTS_PER_T
             h = handles.long()
             who = played[h[:, 0], h[:, 1], h[:, 2]]                                        # [B] the member that played each transition
             row = []
-            for p in range(2):
-                with torch.no_grad():
-                    nxt = tpop.expanded(next_state, who, p)                                # [B, 12, 5]: each transition through its member's target
-                    nxt = torch.where(not_done[:, None, None], nxt, torch.zeros_like(nxt))
-                    estimated = nxt.amax(2).mean(1) * (GAMMA ** N_STEP) + reward
-                for m in range(K):
-                    mine = ((h[:, 2] == p) & (who == m)).to(estimated.dtype)
-                    predicted = policies[p][m](swarm_obs).gather(1, action.unsqueeze(1)).squeeze(1)
-                    loss = (F.smooth_l1_loss(predicted, estimated, reduction="none") * mine).sum() / mine.sum().clamp(min=1.0)
-                    opts[p][m].zero_grad()
-                    loss.backward()
-                    for w in policies[p][m].parameters():
-                        w.grad.data.clamp_(-1, 1)
-                    opts[p][m].step()
-                    row.append(loss.detach())
-            losses.append(torch.stack(row).view(2, K))
+            if device_learner:
+                for p in range(2):                                                         # seat p's rows keep their member, the others are nobody's
+                    row.append(learners[p].step_on((swarm_obs, action, next_state, reward, not_done), torch.where(h[:, 2] == p, who, nobody)).clone())
+                losses.append(torch.stack(row))
+            else:
+                for p in range(2):
+                    with torch.no_grad():
+                        nxt = tpop.expanded(next_state, who, p)                                # [B, 12, 5]: each transition through its member's target
+                        nxt = torch.where(not_done[:, None, None], nxt, torch.zeros_like(nxt))
+                        estimated = nxt.amax(2).mean(1) * (GAMMA ** N_STEP) + reward
+                    for m in range(K):
+                        mine = ((h[:, 2] == p) & (who == m)).to(estimated.dtype)
+                        predicted = policies[p][m](swarm_obs).gather(1, action.unsqueeze(1)).squeeze(1)
+                        loss = (F.smooth_l1_loss(predicted, estimated, reduction="none") * mine).sum() / mine.sum().clamp(min=1.0)
+                        opts[p][m].zero_grad()
+                        loss.backward()
+                        for w in policies[p][m].parameters():
+                            w.grad.data.clamp_(-1, 1)
+                        opts[p][m].step()
+                        row.append(loss.detach())
+                losses.append(torch.stack(row).view(2, K))
         if t % 100 == 99:
             for p in range(2):
                 for m in range(K):
@@ -92,11 +106,12 @@ def main(num_envs=8192, turns=300, batch=256, seed=1, team_size=NUM_AGENTS_PER_T
     losses = torch.stack(losses).cpu()                                                     # [turns - N_STEP - 1, 2, K]
     mem.check()
     pop.check()
-    tpop.check()
+    if not device_learner:
+        tpop.check()
     counts = pop.counts[:, :K].cpu()
-    print("%d envs x %d turns in %.3f s (%.1f M env-steps/s, networks and learning included); games per member seat 0 %s seat 1 %s, wins %s / %s; "
+    print("%s%d envs x %d turns in %.3f s (%.1f M env-steps/s, networks and learning included); games per member seat 0 %s seat 1 %s, wins %s / %s; "
           "loss of member 0 first %.4g / %.4g last %.4g / %.4g, all finite: %s" % (
-              num_envs, turns, dt, num_envs * turns / dt / 1e6, counts[0, :, 0].tolist(), counts[1, :, 0].tolist(), counts[0, :, 1].tolist(),
+              "device learner: " if device_learner else "", num_envs, turns, dt, num_envs * turns / dt / 1e6, counts[0, :, 0].tolist(), counts[1, :, 0].tolist(), counts[0, :, 1].tolist(),
               counts[1, :, 1].tolist(), float(losses[0, 0, 0]), float(losses[0, 1, 0]), float(losses[-1, 0, 0]), float(losses[-1, 1, 0]),
               bool(torch.isfinite(losses).all())))
     env.close()
@@ -104,5 +119,5 @@ def main(num_envs=8192, turns=300, batch=256, seed=1, team_size=NUM_AGENTS_PER_T
 
 
 if __name__ == "__main__":
-    a = sys.argv[1:]
-    main(int(a[0]) if a else 8192, int(a[1]) if len(a) > 1 else 300, int(a[2]) if len(a) > 2 else 256)
+    a = [x for x in sys.argv[1:] if x != "--device-learner"]
+    main(int(a[0]) if a else 8192, int(a[1]) if len(a) > 1 else 300, int(a[2]) if len(a) > 2 else 256, device_learner="--device-learner" in sys.argv[1:])
