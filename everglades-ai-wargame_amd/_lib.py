@@ -34,6 +34,10 @@ POPLEARN_EXPORTS = ["evg_pop_learn_expand_ids", "evg_pop_learn_take_rows", "evg_
                     "evg_adam_step_grouped"]
 # EVG_POP_LEARN_MAX_PARTIALS, EVG_TD_HEAD_GROUPED_WORKSPACE_BYTES, EVG_POP_LEARN_MAX_TENSORS of include/evg_pop_learn.h
 POP_LEARN_MAX_PARTIALS, TD_HEAD_GROUPED_WORKSPACE_BYTES, POP_LEARN_MAX_TENSORS = 512 + 16, 4 * 1024 * 16, 6
+# `make -C csrc popbf16`: the product plus BF16_EXPORTS plus the two entry points of include/evg_pop_bf16.h (QPopulationBf16 / SmartQPopulationBf16
+# load it: load_popbf16)
+POPBF16_LIB_PATH = os.path.join(HERE, "libevg_popbf16.so")
+POPBF16_EXPORTS = ["evg_population_qnet_bf16", "evg_smart_population_qnet_bf16"]
 STAMPS_LIB_PATH =os.path.join(HERE, "libevg_stamps.so")  # `make -C csrc stamps`: in-kernel phase stamps (tools/stamps.py)
 
 NUM_PLAYERS, NUM_GROUPS, NUM_NODES, NUM_UNITS, NUM_ACTIONS, OBS_LEN = 2, 12, 11, 100, 7, 105
@@ -371,6 +375,9 @@ def load(path=None):
     L.evg_smart_population_clear.argtypes = [vp, sp, vp]
     L.evg_smart_population_assign.argtypes = [vp, sp, vp, vp, vp, vp]
     L.evg_smart_population_qnet.argtypes = [vp, sp, C.c_int, C.c_int64, C.c_int, vp, vp, vp, vp, vp]
+    if hasattr(L, "evg_population_qnet_bf16"):       # libevg_popbf16.so only
+        L.evg_population_qnet_bf16.argtypes = [vp, pp, C.c_int, C.c_int64, C.c_int, vp, vp, vp, vp, vp]
+        L.evg_smart_population_qnet_bf16.argtypes = [vp, sp, C.c_int, C.c_int64, C.c_int, vp, vp, vp, vp, vp]
     L.evg_random_actions_seat.argtypes = [vp, C.c_int, vp, vp]
     L.evg_smart_state_seat.argtypes = [vp, vp, vp, vp]
     L.evg_smart_state_compact.argtypes = [vp, C.c_int, vp, vp, vp, vp]
@@ -427,6 +434,16 @@ def load_bf16():
     missing = [n for n in BF16_EXPORTS if not hasattr(L, n)]
     if missing:
         raise EvgError("%s does not export %s; rebuild it (make -C everglades-ai-wargame_amd/csrc bf16)" % (BF16_LIB_PATH, ", ".join(missing)))
+    return L
+
+
+def load_popbf16():
+    """Load libevg_popbf16.so: libevg.so's sources built with -DEVG_BF16 -DEVG_POP_BF16, which exports the entry points of include/evg.h plus
+    BF16_EXPORTS plus POPBF16_EXPORTS (include/evg_pop_bf16.h).  A handle of libevg.so is valid in it; a failed call's text is its own evg_last_error."""
+    L = load(POPBF16_LIB_PATH)
+    missing = [n for n in BF16_EXPORTS + POPBF16_EXPORTS if not hasattr(L, n)]
+    if missing:
+        raise EvgError("%s does not export %s; rebuild it (make -C everglades-ai-wargame_amd/csrc popbf16)" % (POPBF16_LIB_PATH, ", ".join(missing)))
     return L
 
 

@@ -1572,8 +1572,9 @@ int evg_population_assign(evg_handle* h, const evg_population* pop, const uint8_
     return launched("population assign", launch_population_assign(h->S, *pop, mask, winner, history_out, stream));
 } catch (...) { return on_exception(); }
 
-int evg_population_qnet(evg_handle* h, const evg_population* pop, int layout, int64_t rows, int seat, const uint8_t* member, const float* in0,
-                        const float* in1, float* q_out, void* stream) try {
+// the argument checks of evg_population_qnet and evg_population_qnet_bf16 (include/evg_pop_bf16.h): one statement of the refusals for both precisions
+static int population_qnet_check(evg_handle* h, const evg_population* pop, int layout, int64_t rows, int seat, const uint8_t* member, const float* in0,
+                                 const float* in1, float* q_out) {
     { const int rc = check_population(h, pop, true); if (rc) return rc; }
     if (layout != EVG_QNET_COMPACT && layout != EVG_QNET_COMPACT_SEATS && layout != EVG_QNET_EXPANDED)
         return fail(EVG_ERR_INVALID, "population qnet: unknown layout %d", layout);
@@ -1584,10 +1585,30 @@ int evg_population_qnet(evg_handle* h, const evg_population* pop, int layout, in
     if (!member || !in0 || !q_out || (layout != EVG_QNET_EXPANDED && !in1))
         return fail(EVG_ERR_INVALID, "population qnet: member, in0, q_out and (compact layouts) in1 are required");
     EVG_NEED_ALIGNED16(in0); EVG_NEED_ALIGNED16(in1); EVG_NEED_ALIGNED16(q_out);
+    return EVG_OK;
+}
+
+typedef int (*population_qnet_launch)(const evg_population&, int, long long, int, const uint8_t*, const float*, const float*, float*, int, void*);
+
+static int population_qnet_call(evg_handle* h, const evg_population* pop, int layout, int64_t rows, int seat, const uint8_t* member, const float* in0,
+                                const float* in1, float* q_out, void* stream, population_qnet_launch launch) {
+    { const int rc = population_qnet_check(h, pop, layout, rows, seat, member, in0, in1, q_out); if (rc) return rc; }
     EVG_ON_DEVICE(h);
-    return launched("population qnet", launch_population_qnet(*pop, layout, (long long)rows, layout == EVG_QNET_COMPACT_SEATS ? 0 : seat, member, in0, in1,
-                                                              q_out, h->caps.cus, stream));
+    return launched("population qnet", launch(*pop, layout, (long long)rows, layout == EVG_QNET_COMPACT_SEATS ? 0 : seat, member, in0, in1, q_out,
+                                              h->caps.cus, stream));
+}
+
+int evg_population_qnet(evg_handle* h, const evg_population* pop, int layout, int64_t rows, int seat, const uint8_t* member, const float* in0,
+                        const float* in1, float* q_out, void* stream) try {
+    return population_qnet_call(h, pop, layout, rows, seat, member, in0, in1, q_out, stream, launch_population_qnet);
 } catch (...) { return on_exception(); }
+
+#ifdef EVG_POP_BF16     // include/evg_pop_bf16.h; libevg_popbf16.so only
+int evg_population_qnet_bf16(evg_handle* h, const evg_population* pop, int layout, int64_t rows, int seat, const uint8_t* member, const float* in0,
+                             const float* in1, float* q_out, void* stream) try {
+    return population_qnet_call(h, pop, layout, rows, seat, member, in0, in1, q_out, stream, launch_population_qnet_bf16);
+} catch (...) { return on_exception(); }
+#endif
 
 // ---- Smart_State self-royale (include/evg.h: evg_smart_population_clear / _assign / _qnet) ----
 static int check_smart_population(const evg_handle* h, const evg_smart_population* pop, bool forward) {
@@ -1637,8 +1658,9 @@ int evg_smart_population_assign(evg_handle* h, const evg_smart_population* pop, 
     return launched("smart population assign", launch_smart_population_assign(h->S, *pop, mask, winner, history_out, stream));
 } catch (...) { return on_exception(); }
 
-int evg_smart_population_qnet(evg_handle* h, const evg_smart_population* pop, int layout, int64_t rows, int seat, const uint8_t* member, const float* in0,
-                              const float* in1, float* q_out, void* stream) try {
+// the argument checks of evg_smart_population_qnet and evg_smart_population_qnet_bf16, as population_qnet_check
+static int smart_population_qnet_check(evg_handle* h, const evg_smart_population* pop, int layout, int64_t rows, int seat, const uint8_t* member,
+                                       const float* in0, const float* in1, float* q_out) {
     { const int rc = check_smart_population(h, pop, true); if (rc) return rc; }
     if (layout != EVG_QNET_COMPACT && layout != EVG_QNET_COMPACT_SEATS && layout != EVG_QNET_EXPANDED)
         return fail(EVG_ERR_INVALID, "smart population qnet: unknown layout %d", layout);
@@ -1650,10 +1672,31 @@ int evg_smart_population_qnet(evg_handle* h, const evg_smart_population* pop, in
     if (!member || !in0 || !q_out || (layout != EVG_QNET_EXPANDED && !in1))
         return fail(EVG_ERR_INVALID, "smart population qnet: member, in0, q_out and (compact layouts) in1 are required");
     EVG_NEED_ALIGNED16(in0); EVG_NEED_ALIGNED16(in1); EVG_NEED_ALIGNED16(q_out);
+    return EVG_OK;
+}
+
+typedef int (*smart_population_qnet_launch)(const evg_smart_population&, int, long long, int, const uint8_t*, const float*, const float*, float*, int,
+                                            void*);
+
+static int smart_population_qnet_call(evg_handle* h, const evg_smart_population* pop, int layout, int64_t rows, int seat, const uint8_t* member,
+                                      const float* in0, const float* in1, float* q_out, void* stream, smart_population_qnet_launch launch) {
+    { const int rc = smart_population_qnet_check(h, pop, layout, rows, seat, member, in0, in1, q_out); if (rc) return rc; }
     EVG_ON_DEVICE(h);
-    return launched("smart population qnet", launch_smart_population_qnet(*pop, layout, (long long)rows, layout == EVG_QNET_COMPACT_SEATS ? 0 : seat,
-                                                                          member, in0, in1, q_out, h->caps.cus, stream));
+    return launched("smart population qnet", launch(*pop, layout, (long long)rows, layout == EVG_QNET_COMPACT_SEATS ? 0 : seat, member, in0, in1, q_out,
+                                                    h->caps.cus, stream));
+}
+
+int evg_smart_population_qnet(evg_handle* h, const evg_smart_population* pop, int layout, int64_t rows, int seat, const uint8_t* member, const float* in0,
+                              const float* in1, float* q_out, void* stream) try {
+    return smart_population_qnet_call(h, pop, layout, rows, seat, member, in0, in1, q_out, stream, launch_smart_population_qnet);
 } catch (...) { return on_exception(); }
+
+#ifdef EVG_POP_BF16     // include/evg_pop_bf16.h; libevg_popbf16.so only
+int evg_smart_population_qnet_bf16(evg_handle* h, const evg_smart_population* pop, int layout, int64_t rows, int seat, const uint8_t* member,
+                                   const float* in0, const float* in1, float* q_out, void* stream) try {
+    return smart_population_qnet_call(h, pop, layout, rows, seat, member, in0, in1, q_out, stream, launch_smart_population_qnet_bf16);
+} catch (...) { return on_exception(); }
+#endif
 
 void evg_move_table(int32_t* table /* [11][5] */) {
     // agents/Smart_State/Move_Translation.py:3-97: node reached from (0-indexed) node n0 in direction 0 left, 1 right, 2 up, 3 down, 4 stay

@@ -29,6 +29,9 @@
 #ifdef EVG_BF16
 #include "../../include/evg_qnet_bf16.h"
 #endif
+#ifdef EVG_POP_BF16
+#include "../../include/evg_pop_bf16.h"
+#endif
 #ifdef EVG_GRAD
 #include "../../include/evg_qnet_grad.h"
 #endif
@@ -309,5 +312,12 @@ int launch_smart_population_assign(const DevState& S, const evg_smart_population
                                    void* stream);
 int launch_smart_population_qnet(const evg_smart_population& pop, int layout, long long rows, int seat, const uint8_t* member, const float* in0,
                                  const float* in1, float* q_out, int num_cu, void* stream);
+#ifdef EVG_POP_BF16
+// the grouped forwards on the bf16 matrix cores (population_bf16_kernels.inc, libevg_popbf16.so); validated by the caller as for the fp32 launches
+int launch_population_qnet_bf16(const evg_population& pop, int layout, long long rows, int seat, const uint8_t* member, const float* in0,
+                                const float* in1, float* q_out, int num_cu, void* stream);
+int launch_smart_population_qnet_bf16(const evg_smart_population& pop, int layout, long long rows, int seat, const uint8_t* member, const float* in0,
+                                      const float* in1, float* q_out, int num_cu, void* stream);
+#endif
 
 }  // namespace evg

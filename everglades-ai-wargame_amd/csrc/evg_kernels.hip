@@ -86,6 +86,9 @@ namespace evg {
 #ifdef EVG_BF16                  // `make bf16` (libevg_bf16.so): the product's kernels plus ...
 #include "qnet_bf16_kernels.inc"    // the two Q networks' reduced-precision forward on v_mfma_f32_16x16x32_bf16 (acting, target network)
 #endif
+#ifdef EVG_POP_BF16              // `make popbf16` (libevg_popbf16.so, with EVG_BF16): ... plus ...
+#include "population_bf16_kernels.inc"   // self-royale: the grouped forward of both populations on the bf16 matrix cores
+#endif
 #ifdef EVG_GRAD                  // `make grad` (libevg_grad.so): the product's kernels plus ...
 #include "qnet_grad_kernels.inc"    // the backward pass of the two Q networks' expanded fp32 forward (optimize_model's policy forward)
 #endif

@@ -272,9 +272,10 @@ int launch_population_assign(const DevState& S, const evg_population& pop, const
     return (int)hipGetLastError();
 }
 
-int launch_population_qnet(const evg_population& pop, int layout, long long rows, int seat, const uint8_t* member, const float* in0, const float* in1,
-                           float* q_out, int num_cu, void* stream) {
-    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+// the bucket pass of one call (three launches on s) and the grouped forward's arguments p; -> the forward's grid.  Shared by the fp32 launch below and
+// the bf16 one (population_bf16_kernels.inc)
+static dim3 population_qnet_prepare(const evg_population& pop, int layout, long long rows, int seat, const uint8_t* member, const float* in0,
+                                    const float* in1, float* q_out, int num_cu, hipStream_t s, MiniPopArgs& p) {
     const int S = layout == EVG_QNET_COMPACT_SEATS ? 2 : 1;
     const int team[2] = {S == 2 ? 0 : seat, 1};      // the team that plays seat slot 0 / 1
     PopBucket b;
@@ -286,7 +287,6 @@ int launch_population_qnet(const evg_population& pop, int layout, long long rows
     hipLaunchKernelGGL(evg_population_scan_kernel, dim3((unsigned)S), dim3(256), 0, s, b);
     hipLaunchKernelGGL(evg_population_scatter_kernel, dim3((unsigned)b.nb, (unsigned)S), dim3(POP_BLOCK), 0, s, b);
 
-    MiniPopArgs p;
     for (int t = 0; t < 2; ++t) p.q.set[t] = MiniQnetSet{nullptr, nullptr, nullptr, nullptr};
     p.q.h1 = pop.h1; p.q.final_relu = pop.final_relu; p.q.num_seats = S; p.q.rows = rows; p.q.in0 = in0; p.q.in1 = in1; p.q.out = q_out;
     for (int t = 0; t < 2; ++t)
@@ -302,7 +302,14 @@ int launch_population_qnet(const evg_population& pop, int layout, long long rows
     long long blocks = (groups + QN_WAVES - 1) / QN_WAVES;
     const long long cap = 2LL * (num_cu > 0 ? num_cu : 256);
     if (blocks > cap) blocks = cap;
-    const dim3 grid((unsigned)blocks, (unsigned)(S * p.ky));
+    return dim3((unsigned)blocks, (unsigned)(S * p.ky));
+}
+
+int launch_population_qnet(const evg_population& pop, int layout, long long rows, int seat, const uint8_t* member, const float* in0, const float* in1,
+                           float* q_out, int num_cu, void* stream) {
+    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+    MiniPopArgs p;
+    const dim3 grid = population_qnet_prepare(pop, layout, rows, seat, member, in0, in1, q_out, num_cu, s, p);
     if (layout == EVG_QNET_EXPANDED)
         hipLaunchKernelGGL(evg_mini_qnet_pop_kernel<true>, grid, dim3(64 * QN_WAVES), 0, s, p);
     else
@@ -328,9 +335,9 @@ int launch_smart_population_assign(const DevState& S, const evg_smart_population
     return (int)hipGetLastError();
 }
 
-int launch_smart_population_qnet(const evg_smart_population& pop, int layout, long long rows, int seat, const uint8_t* member, const float* in0,
-                                 const float* in1, float* q_out, int num_cu, void* stream) {
-    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+// population_qnet_prepare for the Smart_State network
+static dim3 smart_population_qnet_prepare(const evg_smart_population& pop, int layout, long long rows, int seat, const uint8_t* member, const float* in0,
+                                          const float* in1, float* q_out, int num_cu, hipStream_t s, SmartPopArgs& p) {
     const int S = layout == EVG_QNET_COMPACT_SEATS ? 2 : 1;
     const int team[2] = {S == 2 ? 0 : seat, 1};      // the team that plays seat slot 0 / 1
     PopBucket b;
@@ -342,7 +349,6 @@ int launch_smart_population_qnet(const evg_smart_population& pop, int layout, lo
     hipLaunchKernelGGL(evg_population_scan_kernel, dim3((unsigned)S), dim3(256), 0, s, b);
     hipLaunchKernelGGL(evg_population_scatter_kernel, dim3((unsigned)b.nb, (unsigned)S), dim3(POP_BLOCK), 0, s, b);
 
-    SmartPopArgs p;
     for (int t = 0; t < 2; ++t) p.q.set[t] = QnetSet{nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
     p.q.h1 = pop.h1; p.q.h2 = pop.h2; p.q.final_relu = pop.final_relu; p.q.num_seats = S; p.q.rows = rows; p.q.in0 = in0; p.q.in1 = in1; p.q.out = q_out;
     for (int t = 0; t < 2; ++t)
@@ -359,7 +365,14 @@ int launch_smart_population_qnet(const evg_smart_population& pop, int layout, lo
     long long blocks = (groups + QN_WAVES - 1) / QN_WAVES;
     const long long cap = 2LL * (num_cu > 0 ? num_cu : 256);
     if (blocks > cap) blocks = cap;
-    const dim3 grid((unsigned)blocks, (unsigned)(S * p.ky));
+    return dim3((unsigned)blocks, (unsigned)(S * p.ky));
+}
+
+int launch_smart_population_qnet(const evg_smart_population& pop, int layout, long long rows, int seat, const uint8_t* member, const float* in0,
+                                 const float* in1, float* q_out, int num_cu, void* stream) {
+    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+    SmartPopArgs p;
+    const dim3 grid = smart_population_qnet_prepare(pop, layout, rows, seat, member, in0, in1, q_out, num_cu, s, p);
     if (layout == EVG_QNET_EXPANDED)
         hipLaunchKernelGGL(evg_qnet_pop_kernel<true>, grid, dim3(64 * QN_WAVES), 0, s, p);
     else

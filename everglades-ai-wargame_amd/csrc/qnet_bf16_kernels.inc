@@ -2,6 +2,8 @@
 // for acting and for the target network: every layer on v_mfma_f32_16x16x32_bf16.  Included by evg_kernels.hip (namespace evg) under EVG_BF16
 // (`make bf16`, libevg_bf16.so), after qnet_kernels.inc and minimized_qnet.inc, whose argument structs (QnetArgs, MiniQnetArgs), qn_f4 and qn_relu it
 // shares; the fp32 evaluators are not touched.
+// The two kernels' bodies are qnet_bf16_body.inc and minimized_qnet_bf16_body.inc (QB_GROUPED 0): program text that the grouped kernels of
+// population_bf16_kernels.inc include as well (QB_GROUPED 1).
 //
 //   evg_qnet_bf16_kernel<EXPANDED>        59 -> h1 -> h2 -> 5, h1, h2 in 1..64
 //   evg_mini_qnet_bf16_kernel<EXPANDED>   59 -> h1 -> 11, h1 in 1..128
@@ -161,69 +163,9 @@ __global__ void __launch_bounds__(64 * QN_WAVES) evg_qnet_bf16_kernel(QnetArgs a
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int seat = blockIdx.y;
     const QnetSet W = a.set[seat];
-    const int H1 = a.h1, H2 = a.h2, S = a.num_seats;
-    qb_stage<QB_NATURAL>(w1s, W.w1, QN_IN, H1, EXPANDED ? QN_IN : 34, 4, 2, tid);
-    if (!EXPANDED) qb_stage<QB_SWARM>(w1s + 8 * 64, W.w1, QN_IN, H1, QN_IN, 4, 1, tid);
-    qb_stage<QB_CHAINED>(w2s, W.w2, H1, H2, H1, 4, 2, tid);
-    qb_stage<QB_CHAINED>(w3s, W.w3, H2, QN_OUT, H2, 1, 2, tid);
-    __syncthreads();
-
-    const int n = lane & 15, q = lane >> 4;
-    qb_bf8 w1f[4][EXPANDED ? 2 : 1], w2f[4][2], w3f[2];      // (the compact prefix's 8 fragments run once per 16 envs: read from LDS there)
-    qn_f4 b1v[4], b2v[4];
-#pragma unroll
-    for (int t = 0; t < 4; ++t) {
-        if (EXPANDED) {
-            w1f[t][0] = w1s[(2 * t) * 64 + lane];
-            w1f[t][EXPANDED ? 1 : 0] = w1s[(2 * t + 1) * 64 + lane];
-        } else {
-            w1f[t][0] = w1s[(8 + t) * 64 + lane];
-        }
-        w2f[t][0] = w2s[(2 * t) * 64 + lane];
-        w2f[t][1] = w2s[(2 * t + 1) * 64 + lane];
-        b1v[t] = qb_bias(W.b1, H1, t, q);
-        b2v[t] = qb_bias(W.b2, H2, t, q);
-    }
-    w3f[0] = w3s[lane];
-    w3f[1] = w3s[64 + lane];
-    const qn_f4 b3v = qb_bias(W.b3, QN_OUT, 0, q);
-
-    const long long R = a.rows, groups = (R + 15) >> 4;
-    for (long long g = (long long)blockIdx.x * QN_WAVES + wave; g < groups; g += (long long)gridDim.x * QN_WAVES) {
-        const long long ra = (g << 4) + n;                // this lane's row: column n of every tile
-        const bool va = ra < R;
-        const long long rc = va ? ra : R - 1;             // the row this lane reads: its own, or (past the end) the last one, whose values it drops
-        if (EXPANDED) {
-            const float* x = a.in0 + rc * QN_IN;
-            const qb_bf8 x0 = qb_load8(x, 8 * q, QN_IN, va), x1 = qb_load8(x, 32 + 8 * q, QN_IN, va);
-            qn_f4 acc[4];
-#pragma unroll
-            for (int t = 0; t < 4; ++t) acc[t] = qb_mfma(w1f[t][EXPANDED ? 1 : 0], x1, qb_mfma(w1f[t][0], x0, b1v[t]));
-            const qn_f4 out = qb_smart_tail(acc, w2f, w3f, b2v, b3v, H1, H2, a.final_relu, q);
-            qb_store_q<QN_OUT>(a.out + rc * QN_OUT + 4 * q, out, q, va);
-        } else {
-            const long long vr = rc * S + seat;          // the row of (env, seat) in [R][S][...]
-            const float* sh = a.in0 + vr * 34;
-            const float* sw = a.in1 + vr * (12 * 13);
-            qb_bf4 xs[12];                                // every swarm's features, in flight from here on
-#pragma unroll
-            for (int s = 0; s < 12; ++s) xs[s] = qb_load_swarm(sw + 13 * s, q, va);
-            const qb_bf8 p0 = qb_load8(sh, 8 * q, 34, va), p1 = qb_load8(sh, 32 + 8 * q, 34, va);
-            qn_f4 pre[4];                                 // b1 + the 34 shared terms, once per env
-#pragma unroll
-            for (int t = 0; t < 4; ++t) pre[t] = qb_mfma(w1s[(2 * t + 1) * 64 + lane], p1, qb_mfma(w1s[(2 * t) * 64 + lane], p0, b1v[t]));
-            float* o = a.out + vr * (12 * QN_OUT) + 4 * q;
-#pragma unroll
-            for (int s = 0; s < 12; ++s) {
-                const qb_bf8 xb = qb_swarm_frag(xs[s], s, q);
-                qn_f4 acc[4];
-#pragma unroll
-                for (int t = 0; t < 4; ++t) acc[t] = qb_mfma(w1f[t][0], xb, pre[t]);
-                const qn_f4 out = qb_smart_tail(acc, w2f, w3f, b2v, b3v, H1, H2, a.final_relu, q);
-                qb_store_q<QN_OUT>(o + s * QN_OUT, out, q, va);
-            }
-        }
-    }
+#define QB_GROUPED 0
+#include "qnet_bf16_body.inc"
+#undef QB_GROUPED
 }
 
 int launch_smart_qnet_bf16(const evg_qnet& net, int layout, long long rows, const float* in0, const float* in1, float* q_out, int num_cu, void* stream) {
@@ -277,73 +219,9 @@ __global__ void __launch_bounds__(64 * QN_WAVES, 2) evg_mini_qnet_bf16_kernel(Mi
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int seat = blockIdx.y;
     const MiniQnetSet W = a.set[seat];
-    const int H1 = a.h1, S = a.num_seats;
-    const int nt = (H1 + 15) >> 4;                        // column tiles of the hidden layer
-    qb_stage<QB_NATURAL>(w1s, W.w1, QN_IN, H1, EXPANDED ? QN_IN : 34, nt, 2, tid);
-    if (!EXPANDED) qb_stage<QB_SWARM>(w1s + 2 * MQ_TILES * 64, W.w1, QN_IN, H1, QN_IN, nt, 1, tid);
-    qb_stage<QB_CHAINED>(w2s, W.w2, H1, MQ_OUT, H1, 1, MQ_TILES / 2, tid);
-    for (int i = tid; i < MQ_H; i += 64 * QN_WAVES) b1s[i] = i < H1 ? W.b1[i] : 0.0f;
-    __syncthreads();
-
-    const int n = lane & 15, q = lane >> 4;
-    qb_bf8 swf[EXPANDED ? 1 : MQ_TILES], w2f[MQ_TILES / 2];   // (the other layer-1 fragments are read from LDS at every use)
-#pragma unroll
-    for (int t = 0; t < MQ_TILES; ++t)
-        if (!EXPANDED && t < nt) swf[t] = w1s[(2 * MQ_TILES + t) * 64 + lane];
-#pragma unroll
-    for (int u = 0; u < MQ_TILES / 2; ++u) w2f[u] = w2s[u * 64 + lane];
-    const qn_f4 b2v = qb_bias(W.b2, MQ_OUT, 0, q);
-    const qn_f4 zero = qn_f4{0.0f, 0.0f, 0.0f, 0.0f};
-
-    const long long R = a.rows, groups = (R + 15) >> 4;
-    for (long long g = (long long)blockIdx.x * QN_WAVES + wave; g < groups; g += (long long)gridDim.x * QN_WAVES) {
-        const long long ra = (g << 4) + n;                // this lane's row: column n of every tile
-        const bool va = ra < R;
-        const long long rc = va ? ra : R - 1;             // the row this lane reads: its own, or (past the end) the last one, whose values it drops
-        if (EXPANDED) {
-            const float* x = a.in0 + rc * QN_IN;
-            const qb_bf8 x0 = qb_load8(x, 8 * q, QN_IN, va), x1 = qb_load8(x, 32 + 8 * q, QN_IN, va);
-            qn_f4 acc[MQ_TILES];
-#pragma unroll
-            for (int t = 0; t < MQ_TILES; ++t) {
-                acc[t] = zero;
-                if (t < nt)
-                    acc[t] = qb_mfma(w1s[(2 * t + 1) * 64 + lane], x1,
-                                     qb_mfma(w1s[(2 * t) * 64 + lane], x0, *reinterpret_cast<const qn_f4*>(b1s + 16 * t + 4 * q)));
-            }
-            const qn_f4 out = qb_mini_tail(acc, w2f, b2v, H1, nt, a.final_relu, q);
-            qb_store_q<MQ_OUT>(a.out + rc * MQ_OUT + 4 * q, out, q, va);
-        } else {
-            const long long vr = rc * S + seat;          // the row of (env, seat) in [R][S][...]
-            const float* sh = a.in0 + vr * 34;
-            const float* sw = a.in1 + vr * (12 * 13);
-            qb_bf4 xs[12];                                // every swarm's features, in flight from here on
-#pragma unroll
-            for (int s = 0; s < 12; ++s) xs[s] = qb_load_swarm(sw + 13 * s, q, va);
-            const qb_bf8 p0 = qb_load8(sh, 8 * q, 34, va), p1 = qb_load8(sh, 32 + 8 * q, 34, va);
-            qn_f4 pre[MQ_TILES];                          // b1 + the 34 shared terms, once per env
-#pragma unroll
-            for (int t = 0; t < MQ_TILES; ++t) {
-                pre[t] = zero;
-                if (t < nt)
-                    pre[t] = qb_mfma(w1s[(2 * t + 1) * 64 + lane], p1,
-                                     qb_mfma(w1s[(2 * t) * 64 + lane], p0, *reinterpret_cast<const qn_f4*>(b1s + 16 * t + 4 * q)));
-            }
-            float* o = a.out + vr * (12 * MQ_OUT) + 4 * q;
-#pragma unroll
-            for (int s = 0; s < 12; ++s) {
-                const qb_bf8 xb = qb_swarm_frag(xs[s], s, q);
-                qn_f4 acc[MQ_TILES];
-#pragma unroll
-                for (int t = 0; t < MQ_TILES; ++t) {
-                    acc[t] = zero;
-                    if (t < nt) acc[t] = qb_mfma(swf[t], xb, pre[t]);
-                }
-                const qn_f4 out = qb_mini_tail(acc, w2f, b2v, H1, nt, a.final_relu, q);
-                qb_store_q<MQ_OUT>(o + s * MQ_OUT, out, q, va);
-            }
-        }
-    }
+#define QB_GROUPED 0
+#include "minimized_qnet_bf16_body.inc"
+#undef QB_GROUPED
 }
 
 int launch_minimized_qnet_bf16(const evg_mini_qnet& net, int layout, long long rows, const float* in0, const float* in1, float* q_out, int num_cu,

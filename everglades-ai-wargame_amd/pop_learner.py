@@ -26,11 +26,16 @@ allocated at the first call with a given batch size; after that a step allocates
 inside a captured torch.cuda.graph.  `lr` is read at every step.  There is no step(batch_size, seed): the ring that records who played a transition is
 the caller's, and a prioritized memory is served through weights= and the returned priorities.
 
-target_precision="bf16" evaluates the target (and, in "double_mean", the selecting) networks on the bf16 matrix cores (include/evg_qnet_bf16.h).  The
-grouped forwards are fp32, so this path has no populations for them (target_pop and select_pop are None): each member's SmartQNetBf16 /
-MinimizedQNetBf16 (target_nets, select_nets) evaluates the whole batch into one scratch buffer and evg_pop_learn_take_rows keeps that member's rows --
-2 K launches in place of one grouped forward, K times the forward's arithmetic, every q_next row bit-equal to the member's own bf16 evaluator.  The
-policy forward, the backward and Adam are fp32 whatever the setting.
+target_precision="bf16_grouped" evaluates the target (and, in "double_mean", the selecting) networks on the bf16 matrix cores (include/evg_qnet_bf16.h)
+with one grouped forward each (include/evg_pop_bf16.h): target_pop and select_pop are SmartQPopulationBf16 / QPopulationBf16, target_nets and
+select_nets stay None, and a step has the launches of "fp32".  Every q_next row is bit-equal to the member's own bf16 evaluator.  Measured (DESIGN.md,
+"Population forwards, bf16"): faster than "bf16" at every batch size; against "fp32" faster at B = 16 384 and not at B <= 1 024, where the target
+forward sits on its fixed part.
+
+target_precision="bf16" is the older form of the same numbers, without populations for the targets (target_pop and select_pop are None): each member's
+SmartQNetBf16 / MinimizedQNetBf16 (target_nets, select_nets) evaluates the whole batch into one scratch buffer and evg_pop_learn_take_rows keeps that
+member's rows -- 2 K launches in place of one grouped forward, K times the forward's arithmetic, q_next bit-identical to "bf16_grouped".  The policy
+forward, the backward and Adam are fp32 whatever the setting.
 """
 import ctypes as C
 
@@ -59,8 +64,8 @@ class PopulationLearner(object):
             raise ValueError('kind must be "smart" or "minimized" (got %r)' % (kind,))
         if mode not in _lib.TD_MODES:
             raise ValueError("mode must be one of %s (got %r)" % (", ".join(sorted(_lib.TD_MODES)), mode))
-        if target_precision not in ("fp32", "bf16"):
-            raise ValueError('target_precision must be "fp32" or "bf16" (got %r)' % (target_precision,))
+        if target_precision not in ("fp32", "bf16", "bf16_grouped"):
+            raise ValueError('target_precision must be "fp32" or "bf16" or "bf16_grouped" (got %r)' % (target_precision,))
         if not isinstance(policies, (list, tuple)) or not isinstance(targets, (list, tuple)):
             raise ValueError("policies and targets are lists of networks: one team")
         policies, targets = list(policies), list(targets)
@@ -79,17 +84,18 @@ class PopulationLearner(object):
         n_step = int(n_step)
         if n_step < 1:
             raise ValueError("n_step must be >= 1")
-        from .population import QPopulation, SmartQPopulation
+        from .population import QPopulation, QPopulationBf16, SmartQPopulation, SmartQPopulationBf16
         Pop = SmartQPopulation if kind == "smart" else QPopulation
+        NextPop = Pop if target_precision == "fp32" else (SmartQPopulationBf16 if kind == "smart" else QPopulationBf16)
         self.env, self.kind, self.mode, self.K = env, kind, mode, len(policies)
         self.G = _lib.load_poplearn()
         self.policy_pop = Pop(env, policies, None, final_relu=final_relu, max_rows=1)
         self.target_precision = target_precision
         self.target_pop = self.select_pop = self.target_nets = self.select_nets = None
-        if target_precision == "fp32":
-            self.target_pop = Pop(env, targets, None, final_relu=final_relu, max_rows=1)
+        if target_precision in ("fp32", "bf16_grouped"):                              # one grouped forward each, at that precision
+            self.target_pop = NextPop(env, targets, None, final_relu=final_relu, max_rows=1)
             if mode == "double_mean":
-                self.select_pop = Pop(env, policies, None, final_relu=final_relu, max_rows=1)
+                self.select_pop = NextPop(env, policies, None, final_relu=final_relu, max_rows=1)
             self._targets = self.target_pop.nets[0]
         else:                                                                         # one bf16 evaluator per member; take_rows merges them
             make = env.smart_qnet if kind == "smart" else env.minimized_qnet
@@ -185,8 +191,8 @@ class PopulationLearner(object):
         return out
 
     def next_forward(self, which, next_state, ids12, out, scratch=None):
-        """q of the next-state rows through each row's own member of `which` ("target" or "select") at target_precision: one grouped fp32 forward, or
-        per member a whole-batch bf16 forward into `scratch` and take_rows"""
+        """q of the next-state rows through each row's own member of `which` ("target" or "select") at target_precision: one grouped forward ("fp32",
+        "bf16_grouped"), or ("bf16") per member a whole-batch bf16 forward into `scratch` and take_rows"""
         pop, nets = (self.target_pop, self.target_nets) if which == "target" else (self.select_pop, self.select_nets)
         if pop is not None:
             return pop.expanded(next_state, ids12, 0, out=out)

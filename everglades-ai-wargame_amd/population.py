@@ -262,3 +262,38 @@ class SmartQPopulation(QPopulation):
         self.h1, self.h2 = size
         if desc is not None:
             desc.h1, desc.h2 = size
+
+
+class _Bf16Forward(object):
+    """The grouped forward on the bf16 matrix cores (include/evg_pop_bf16.h, libevg_popbf16.so) in place of the fp32 launch: the one thing the two
+    classes below change.  Assignment, clear, end_of_turn, lists(), state() and load_state() are the fp32 populations' own (libevg.so), so an fp32 and
+    a bf16 population of equal team sizes on one env hold the same members.  A refused call's text is read from the library that refused it."""
+
+    def _launch(self, layout, rows, seat, member, in0, in1, out):
+        ref = self._descriptor(rows)
+        B = _lib.load_popbf16()
+        rc = getattr(B, self._FN + "_qnet_bf16")(self.env._h, ref, layout, rows, int(seat), C.c_void_p(member.data_ptr()), C.c_void_p(in0.data_ptr()),
+                                                 None if in1 is None else C.c_void_p(in1.data_ptr()), C.c_void_p(out.data_ptr()), self.env._stream())
+        if rc:
+            _lib.check(rc, B)
+        return out
+
+
+class QPopulationBf16(_Bf16Forward, QPopulation):
+    """QPopulation whose forwards run on the bf16 matrix cores (evg_population_qnet_bf16): the same four launches, the same published lists, bins and
+    status.  Every Q row equals, bit for bit, what MinimizedQNetBf16 writes for it with that member's weights -- the numeric contract of
+    include/evg_qnet_bf16.h per row, for the acting turn and for a team's target networks.  env.q_population(..., precision="bf16") makes one."""
+
+
+class SmartQPopulationBf16(_Bf16Forward, SmartQPopulation):
+    """SmartQPopulation on the bf16 matrix cores (evg_smart_population_qnet_bf16); see QPopulationBf16.  Every Q row equals, bit for bit, what
+    SmartQNetBf16 writes for it with that member's weights.  env.smart_q_population(..., precision="bf16") makes one."""
+
+
+def make(env, team0, team1, final_relu, max_rows, precision, fp32_cls, bf16_cls):
+    """the population of env.q_population / env.smart_q_population for a precision: "fp32" (the bit-exact chain, the default) or "bf16" """
+    if precision == "fp32":
+        return fp32_cls(env, team0, team1, final_relu=final_relu, max_rows=max_rows)
+    if precision == "bf16":
+        return bf16_cls(env, team0, team1, final_relu=final_relu, max_rows=max_rows)
+    raise ValueError('precision must be "fp32" or "bf16" (got %r)' % (precision,))

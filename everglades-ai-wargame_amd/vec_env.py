@@ -593,18 +593,20 @@ class EvergladesVecEnv(object):
         from . import qnet
         return qnet.make(self, net, final_relu, precision, qnet.MinimizedQNet, qnet.MinimizedQNetBf16)
 
-    def q_population(self, team0, team1=None, final_relu=None, max_rows=None):
+    def q_population(self, team0, team1=None, final_relu=None, max_rows=None, precision="fp32"):
         """Self-royale (everglades_amd.QPopulation; evg_population): two teams of Minimized Q networks, a member per env and seat drawn each episode --
-        `pop(shared, swarm)` -> the q [N, 2, 12, 11] step_q() takes, `pop.end_of_turn()` behind the step.  team1=None plays team0 on both seats."""
-        from .population import QPopulation
-        return QPopulation(self, team0, team1, final_relu=final_relu, max_rows=max_rows)
+        `pop(shared, swarm)` -> the q [N, 2, 12, 11] step_q() takes, `pop.end_of_turn()` behind the step.  team1=None plays team0 on both seats.
+        precision="bf16" returns a QPopulationBf16: the same calls with the forwards on the bf16 matrix cores (include/evg_pop_bf16.h)."""
+        from . import population
+        return population.make(self, team0, team1, final_relu, max_rows, precision, population.QPopulation, population.QPopulationBf16)
 
-    def smart_q_population(self, team0, team1=None, final_relu=None, max_rows=None):
+    def smart_q_population(self, team0, team1=None, final_relu=None, max_rows=None, precision="fp32"):
         """Smart_State self-royale (everglades_amd.SmartQPopulation; evg_smart_population): two teams of Smart_State Q networks (whatever smart_qnet()
         accepts, one (h1, h2) and one final_relu), a member per env and seat drawn each episode -- `pop(shared, swarm)` -> the q [N, 2, 12, 5] step_q()
-        takes, `pop.end_of_turn()` behind the step, `pop.expanded(x, member, seat)` for the target networks.  team1=None plays team0 on both seats."""
-        from .population import SmartQPopulation
-        return SmartQPopulation(self, team0, team1, final_relu=final_relu, max_rows=max_rows)
+        takes, `pop.end_of_turn()` behind the step, `pop.expanded(x, member, seat)` for the target networks.  team1=None plays team0 on both seats.
+        precision="bf16" returns a SmartQPopulationBf16: the same calls with the forwards on the bf16 matrix cores (include/evg_pop_bf16.h)."""
+        from . import population
+        return population.make(self, team0, team1, final_relu, max_rows, precision, population.SmartQPopulation, population.SmartQPopulationBf16)
 
     def smart_replay(self, capacity_turns, n_step=1, gamma=0.999, shaping="normalized_score", seats=0, episode_base=0):
         """The Smart_State learner's n-step replay memory on the device for this env (everglades_amd.SmartReplay: Multi_Step.NStepModule +
@@ -646,7 +648,7 @@ class EvergladesVecEnv(object):
     def smart_population_learner(self, policies, targets, **kw):
         """Self-royale's optimize_model for one team of Smart_State networks on this env's device (everglades_amd.PopulationLearner;
         include/evg_pop_learn.h): `policies` and `targets` are lists of K networks (1..16) as smart_qnet() takes them, one (h1, h2) and one final_relu.
-        Keywords: smart_learner()'s without `beta`.  learner.step_on(batch, member) trains every member on the rows it played (member uint8 [B]; an id
+        Keywords: smart_learner()'s without `beta`; target_precision also takes "bf16_grouped" (the targets as one grouped bf16 forward).  learner.step_on(batch, member) trains every member on the rows it played (member uint8 [B]; an id
         >= K is nobody of this team) in one chain of launches without a torch op.  Create it after env.reset()."""
         from .pop_learner import PopulationLearner
         return PopulationLearner(self, "smart", policies, targets, **kw)

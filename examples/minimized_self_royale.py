@@ -12,11 +12,14 @@ member[e, p], evaluates every env through its own member in one grouped forward,
 Where this departs from the script: one batch is drawn for all eight learners and split by (seat, member), where the script draws one batch per agent
 that played; a member with no transition in the batch takes a zero loss and no step.  A DQN loss need not decrease.
 
-    python examples/minimized_self_royale.py [envs] [turns] [batch] [--device-learner]
+    python examples/minimized_self_royale.py [envs] [turns] [batch] [--device-learner] [--acting-precision {fp32,bf16}]
 
 --device-learner: the learning block is two PopulationLearners (everglades_amd.PopulationLearner, one per seat's team): one step_on per seat trains
 every member on the rows it played, with the other seat's rows passed as id 255 -- no torch forward, backward or optimizer.  There a member without
 a row in the batch really takes no step (the torch loop's zero-gradient opt.step() still moves its parameters through Adam's moments).
+
+--acting-precision bf16: the acting populations evaluate on the bf16 matrix cores (QPopulationBf16 / SmartQPopulationBf16, include/evg_pop_bf16.h); with
+--device-learner the learners' targets do too, as one grouped forward each (target_precision="bf16_grouped").  The policy forward that is trained stays fp32.
 """
 import os
 import sys
@@ -32,7 +35,7 @@ from minimized_training import GAMMA, LR, N_STEP, make_qnet
 NUM_AGENTS_PER_TEAM = 4
 
 
-def main(num_envs=8192, turns=300, batch=256, seed=1, team_size=NUM_AGENTS_PER_TEAM, device_learner=False):
+def main(num_envs=8192, turns=300, batch=256, seed=1, team_size=NUM_AGENTS_PER_TEAM, device_learner=False, acting_precision="fp32"):
     env = evg.EvergladesVecEnv(num_envs, seed=seed, auto_reset=True)
     dev, K = env.device, team_size
     policies = [[make_qnet(dev, 10 * p + m) for m in range(K)] for p in range(2)]
@@ -41,9 +44,10 @@ def main(num_envs=8192, turns=300, batch=256, seed=1, team_size=NUM_AGENTS_PER_T
     eps_table = torch.stack([torch.linspace(0.1, 0.4, K), torch.linspace(0.4, 0.1, K)]).to(dev)
     mem = env.smart_replay(8, n_step=N_STEP, gamma=GAMMA, shaping="custom", seats=(0, 1))
     obs = env.reset()
-    pop = env.q_population(policies[0], policies[1])                                       # the acting networks, drawn per env and episode
+    pop = env.q_population(policies[0], policies[1], precision=acting_precision)          # the acting networks, drawn per env and episode
     if device_learner:                                                                     # one learner per seat's team; it owns the target forward
-        learners = [env.minimized_population_learner(policies[p], targets[p], lr=LR, gamma=GAMMA, n_step=N_STEP, mode="max_mean", clamp=1.0)
+        learners = [env.minimized_population_learner(policies[p], targets[p], lr=LR, gamma=GAMMA, n_step=N_STEP, mode="max_mean", clamp=1.0,
+                                                     target_precision="bf16_grouped" if acting_precision == "bf16" else "fp32")
                     for p in range(2)]
         nobody = torch.full((batch,), 255, dtype=torch.uint8, device=dev)
     else:
@@ -118,4 +122,13 @@ def main(num_envs=8192, turns=300, batch=256, seed=1, team_size=NUM_AGENTS_PER_T
 
 if __name__ == "__main__":
     a = [x for x in sys.argv[1:] if x != "--device-learner"]
-    main(int(a[0]) if a else 8192, int(a[1]) if len(a) > 1 else 300, int(a[2]) if len(a) > 2 else 256, device_learner="--device-learner" in sys.argv[1:])
+    precision = "fp32"                                    # --acting-precision {fp32,bf16}
+    for i, x in enumerate(a):
+        if x == "--acting-precision" or x.startswith("--acting-precision="):
+            precision = x.split("=", 1)[1] if "=" in x else a[i + 1]
+            del a[i:i + (1 if "=" in x else 2)]
+            break
+    if precision not in ("fp32", "bf16"):
+        sys.exit("--acting-precision must be fp32 or bf16")
+    main(int(a[0]) if a else 8192, int(a[1]) if len(a) > 1 else 300, int(a[2]) if len(a) > 2 else 256, device_learner="--device-learner" in sys.argv[1:],
+         acting_precision=precision)
