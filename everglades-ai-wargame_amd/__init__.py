@@ -11,6 +11,7 @@ from .tables import default_tables, tables_from_json
 from .vec_env import EvergladesVecEnv
 from .replay import SmartReplay, PrioritizedSmartReplay
 from .qnet import MinimizedQNet, MinimizedQNetBf16, SmartQNet, SmartQNetBf16
+from .dqn import DqnQNet
 from .learner import DqnLearner
 from .pop_learner import PopulationLearner
 from .league import OpponentLeague
@@ -20,7 +21,7 @@ from .env import EvergladesEnv, canonical_actions
 from .distributed import shard_range, gather_episode_results, win_counts, ResultGather, NativeGather
 from .harness import evaluate, evaluate_all, proportion_confint_normal
 
-__all__ = ["EvergladesVecEnv", "SmartReplay", "PrioritizedSmartReplay", "SmartQNet", "MinimizedQNet", "SmartQNetBf16", "MinimizedQNetBf16", "DqnLearner", "PopulationLearner", "OpponentLeague", "QPopulation", "SmartQPopulation", "QPopulationBf16", "SmartQPopulationBf16", "PipelinedVecEnv", "EvergladesEnv", "EvgError", "EvgFault", "load_library", "default_tables", "tables_from_json",
+__all__ = ["EvergladesVecEnv", "SmartReplay", "PrioritizedSmartReplay", "SmartQNet", "MinimizedQNet", "SmartQNetBf16", "MinimizedQNetBf16", "DqnQNet", "DqnLearner", "PopulationLearner", "OpponentLeague", "QPopulation", "SmartQPopulation", "QPopulationBf16", "SmartQPopulationBf16", "PipelinedVecEnv", "EvergladesEnv", "EvgError", "EvgFault", "load_library", "default_tables", "tables_from_json",
            "canonical_actions", "shard_range", "gather_episode_results", "win_counts", "ResultGather", "NativeGather", "evaluate", "evaluate_all",
            "proportion_confint_normal"]
 

@@ -1340,6 +1340,51 @@ int evg_minimized_qnet_backward(evg_handle* h, const evg_mini_qnet* net, int64_t
 } catch (...) { return on_exception(); }
 #endif
 
+#ifdef EVG_DQN      // include/evg_dqn.h; libevg_dqn.so only
+// ---- the agents/DQN family's acting turn: the 105-h1-132 network, filter_actions, epsilon_greedy ----
+int evg_dqn_qnet(evg_handle* h, const evg_dqn_net* net, int input, int seat, int64_t rows, const void* x, float* q_out, void* stream) try {
+    if (!h || !net) return fail(EVG_ERR_INVALID, "null handle or network descriptor");
+    if (net->struct_size != sizeof(evg_dqn_net))
+        return fail(EVG_ERR_INVALID, "dqn qnet: struct_size %u != sizeof(evg_dqn_net) %zu", net->struct_size, sizeof(evg_dqn_net));
+    if (net->h1 < 1 || net->h1 > EVG_DQN_MAX_HIDDEN)
+        return fail(EVG_ERR_INVALID, "dqn qnet: the hidden size must lie in 1..%d (got %d)", EVG_DQN_MAX_HIDDEN, net->h1);
+    if (net->final_relu != 0 && net->final_relu != 1) return fail(EVG_ERR_INVALID, "dqn qnet: final_relu must be 0 or 1 (got %d)", net->final_relu);
+    if (input != EVG_DQN_ROWS && input != EVG_DQN_OBS_SEAT && input != EVG_DQN_OBS) return fail(EVG_ERR_INVALID, "dqn qnet: unknown input form %d", input);
+    if (input == EVG_DQN_OBS && (seat < 0 || seat > 1)) return fail(EVG_ERR_INVALID, "dqn qnet: seat must be 0 or 1 (got %d)", seat);
+    if (rows < 1 || rows > EVG_QNET_MAX_ROWS) return fail(EVG_ERR_INVALID, "dqn qnet: rows must lie in 1..2^30 (got %lld)", (long long)rows);
+    const float* w[4] = {net->w1, net->b1, net->w2, net->b2};
+    static const char* names[4] = {"w1", "b1", "w2", "b2"};
+    for (int i = 0; i < 4; ++i) {
+        if (!w[i]) return fail(EVG_ERR_INVALID, "dqn qnet: %s is NULL", names[i]);
+        if (misaligned16(w[i])) return fail(EVG_ERR_INVALID, "dqn qnet: %s must be 16-byte aligned (got %p)", names[i], (const void*)w[i]);
+    }
+    if (!x || !q_out) return fail(EVG_ERR_INVALID, "dqn qnet: x and q_out are required");
+    EVG_NEED_ALIGNED16(x); EVG_NEED_ALIGNED16(q_out);
+    EVG_ON_DEVICE(h);
+    const int dtype = input == EVG_DQN_ROWS ? (int)EVG_OBS_F32 : h->cfg.obs_dtype;
+    const long long stride = input == EVG_DQN_OBS ? 2 * EVG_OBS_LEN : EVG_OBS_LEN, offset = input == EVG_DQN_OBS ? seat * EVG_OBS_LEN : 0;
+    return launched("dqn qnet", launch_dqn_qnet(*net, (long long)rows, x, dtype, stride, offset, q_out, stream));
+} catch (...) { return on_exception(); }
+
+int evg_dqn_actions(evg_handle* h, const float* q, int32_t* actions_out, void* stream) try {
+    if (!h || !q || !actions_out) return fail(EVG_ERR_INVALID, "bad argument");
+    EVG_NEED_ALIGNED16(q); EVG_NEED_ALIGNED16(actions_out);
+    EVG_ON_DEVICE(h);
+    return launched("dqn_actions", launch_dqn_actions(h->S, q, actions_out, stream, nullptr, nullptr));
+} catch (...) { return on_exception(); }
+
+int evg_dqn_get_action(evg_handle* h, const float* q, float epsilon, const float* epsilon_env, int seat, int32_t* actions_out, uint8_t* explored_out,
+                       void* stream) try {
+    if (!h || !q || !actions_out || seat < 0 || seat > 1) return fail(EVG_ERR_INVALID, "bad argument");
+    if (const int rc = check_epsilon(epsilon, epsilon_env)) return rc;
+    EVG_NEED_ALIGNED16(q); EVG_NEED_ALIGNED16(actions_out);
+    if (const int rc = check_keyed_philox(h, "evg_dqn_get_action", " (the agent's draws are keyed)")) return rc;
+    EVG_ON_DEVICE(h);
+    const SmartExplore ex{seat, epsilon, epsilon_env, explored_out};
+    return launched("dqn_get_action", launch_dqn_actions(h->S, q, actions_out, stream, &ex, explored_out));
+} catch (...) { return on_exception(); }
+#endif
+
 #ifdef EVG_LEARN    // include/evg_learn.h; libevg_learn.so only
 static int learn_pointer(const char* what, const char* name, const void* p, bool required) {
     if (!p) return required ? fail(EVG_ERR_INVALID, "%s: %s is NULL", what, name) : EVG_OK;

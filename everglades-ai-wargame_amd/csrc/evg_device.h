@@ -41,6 +41,9 @@
 #ifdef EVG_POP_LEARN
 #include "../../include/evg_pop_learn.h"
 #endif
+#ifdef EVG_DQN
+#include "../../include/evg_dqn.h"
+#endif
 #include "evg_rng.h"
 
 namespace evg {
@@ -300,6 +303,14 @@ int launch_td_head_grouped(const evg_td_head_grouped_args& a, void* stream);
 int launch_smart_population_backward(const evg_pop_backward_args& a, int num_cu, void* stream);
 int launch_population_backward(const evg_pop_backward_args& a, int num_cu, void* stream);
 int launch_adam_step_grouped(const evg_adam_grouped_args& a, void* stream);
+#endif
+#ifdef EVG_DQN
+// the agents/DQN family's acting turn (dqn_kernels.inc, libevg_dqn.so); validated by the caller.  x_stride / x_offset: elements from one row's first
+// input to the next row's, and from x to the first row's
+int launch_dqn_qnet(const evg_dqn_net& net, long long rows, const void* x, int obs_dtype, long long x_stride, long long x_offset, float* q_out,
+                    void* stream);
+int launch_dqn_actions(const DevState& S, const float* q, int32_t* actions, void* stream, const SmartExplore* explore /* NULL: filter_actions only */,
+                       uint8_t* explored /* device [N] or NULL */);
 #endif
 // self-royale (population_kernels.inc); `pop` and the sizes are validated by the caller (evg_abi.hip)
 int launch_population_clear(const DevState& S, const evg_population& pop, void* stream);

@@ -98,6 +98,10 @@ namespace evg {
 #ifdef EVG_POP_LEARN             // `make poplearn` (libevg_poplearn.so, with EVG_GRAD and EVG_LEARN): ... plus ...
 #include "pop_learn_kernels.inc"    // self-royale: the grouped TD head, backward and Adam that train every member of a team from one batch
 #endif
+#ifdef EVG_DQN                   // `make dqn` (libevg_dqn.so): the product's kernels plus ...
+#include "dqn_decode.inc"           // the agents/DQN family's decode of its 132-way head (filter_actions) and its exploring draws
+#include "dqn_kernels.inc"          // ... and its 105 -> h1 <= 528 -> 132 network, the hidden layer streamed in chunks, on v_mfma_f32_16x16x4_f32
+#endif
 
 // ---------------------------------------------------------------------------------------------
 // launchers

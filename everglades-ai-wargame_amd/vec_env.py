@@ -593,6 +593,28 @@ class EvergladesVecEnv(object):
         from . import qnet
         return qnet.make(self, net, final_relu, precision, qnet.MinimizedQNet, qnet.MinimizedQNetBf16)
 
+    def dqn_qnet(self, net, final_relu=None):
+        """The agents/DQN family's Q network on this env's device, one launch per call (everglades_amd.DqnQNet, evg_dqn_qnet; include/evg_dqn.h): `net` is
+        the reference's QNetwork(105, 132, seed) (fc1 / fc2, final ReLU), an nn.Sequential Linear(105, h)/ReLU/Linear(h, 132)[/ReLU], or a 4-tuple
+        (w1, b1, w2, b2) with final_relu; h in 1..528.  `qnet(obs, seat=None)` reads the env's observation tensors in their own dtype, `qnet.rows(x)`
+        float32 rows.  Its parameters are read in place on every call; the output has no autograd."""
+        from . import dqn
+        return dqn.DqnQNet(self, net, final_relu=final_relu)
+
+    def dqn_actions(self, q, out=None):
+        """DQNAgent.filter_actions of agents/DQN on the device (evg_dqn_actions; agents/DQN/DQNAgent.py:161-197): `q` float32 [N, 132], Q[group * 11 +
+        node].  Returns int32 [N, 7, 2] {unit, node} with node in 0..10 as the reference returns it, every quirk of its triple loop kept."""
+        from . import dqn
+        return dqn.actions(self, q, out=out)
+
+    def dqn_get_action(self, q, epsilon, seat=0, out=None, explored=None):
+        """DQNAgent.epsilon_greedy of agents/DQN on the device (evg_dqn_get_action; :131-159): per env the coin -- it explores iff coin <= epsilon --, then 7
+        distinct units and 7 distinct nodes 0..10, or dqn_actions.  `epsilon`: a float in [0, 1] for every env, or a float32 tensor [N] (the decay
+        schedule stays the caller's); `seat` keys the draws; `explored`: a uint8 tensor [N] that receives 1 where the random branch ran.  Returns int32
+        [N, 7, 2]: what step_vs() takes as `actions`."""
+        from . import dqn
+        return dqn.get_action(self, q, epsilon, seat=seat, out=out, explored=explored)
+
     def q_population(self, team0, team1=None, final_relu=None, max_rows=None, precision="fp32"):
         """Self-royale (everglades_amd.QPopulation; evg_population): two teams of Minimized Q networks, a member per env and seat drawn each episode --
         `pop(shared, swarm)` -> the q [N, 2, 12, 11] step_q() takes, `pop.end_of_turn()` behind the step.  team1=None plays team0 on both seats.
