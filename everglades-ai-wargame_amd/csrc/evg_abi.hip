@@ -1385,6 +1385,44 @@ int evg_dqn_get_action(evg_handle* h, const float* q, float epsilon, const float
 } catch (...) { return on_exception(); }
 #endif
 
+#ifdef EVG_DQN_GRAD // include/evg_dqn_grad.h; libevg_dqngrad.so only
+// ---- the backward pass of the 105-h1-132 network: the descriptor checks are evg_dqn_qnet's ----
+int evg_dqn_qnet_backward(evg_handle* h, const evg_dqn_net* net, int64_t rows, const float* x, const float* q, const float* gq, const evg_dqn_grads* grads,
+                          void* workspace, int64_t workspace_bytes, float clamp, void* stream) try {
+    if (!h || !net) return fail(EVG_ERR_INVALID, "null handle or network descriptor");
+    if (net->struct_size != sizeof(evg_dqn_net))
+        return fail(EVG_ERR_INVALID, "dqn qnet backward: struct_size %u != sizeof(evg_dqn_net) %zu", net->struct_size, sizeof(evg_dqn_net));
+    if (net->h1 < 1 || net->h1 > EVG_DQN_MAX_HIDDEN)
+        return fail(EVG_ERR_INVALID, "dqn qnet backward: the hidden size must lie in 1..%d (got %d)", EVG_DQN_MAX_HIDDEN, net->h1);
+    if (net->final_relu != 0 && net->final_relu != 1)
+        return fail(EVG_ERR_INVALID, "dqn qnet backward: final_relu must be 0 or 1 (got %d)", net->final_relu);
+    if (rows < 1 || rows > EVG_DQN_GRAD_MAX_ROWS)
+        return fail(EVG_ERR_INVALID, "dqn qnet backward: rows must lie in 1..%d (got %lld)", EVG_DQN_GRAD_MAX_ROWS, (long long)rows);
+    if (!grads) return fail(EVG_ERR_INVALID, "dqn qnet backward: null gradient descriptor");
+    if (grads->struct_size != sizeof(evg_dqn_grads))
+        return fail(EVG_ERR_INVALID, "dqn qnet backward: struct_size %u != sizeof(evg_dqn_grads) %zu", grads->struct_size, sizeof(evg_dqn_grads));
+    if (net->final_relu && !q) return fail(EVG_ERR_INVALID, "dqn qnet backward: q is required with final_relu");
+    const struct { const char* name; const void* p; bool required; } ptrs[] = {
+        {"w1", net->w1, true}, {"b1", net->b1, true}, {"w2", net->w2, true}, {"b2", net->b2, true}, {"x", x, true}, {"q", q, false}, {"gq", gq, true},
+        {"the gradient pointer w1", grads->w1, true}, {"the gradient pointer b1", grads->b1, true}, {"the gradient pointer w2", grads->w2, true},
+        {"the gradient pointer b2", grads->b2, true}, {"the workspace", workspace, true}};
+    for (const auto& p : ptrs) {
+        if (!p.p) {
+            if (p.required) return fail(EVG_ERR_INVALID, "dqn qnet backward: %s is NULL", p.name);
+            continue;
+        }
+        if (misaligned16(p.p)) return fail(EVG_ERR_INVALID, "dqn qnet backward: %s must be 16-byte aligned (got %p)", p.name, p.p);
+    }
+    const int64_t need = EVG_DQN_GRAD_WORKSPACE_BYTES(rows, net->h1);
+    if (workspace_bytes < need)
+        return fail(EVG_ERR_INVALID, "dqn qnet backward: the workspace is too small (%lld bytes, %lld rows of h1 %d need %lld)", (long long)workspace_bytes,
+                    (long long)rows, net->h1, (long long)need);
+    if (!(clamp >= 0.0f) || !std::isfinite(clamp)) return fail(EVG_ERR_INVALID, "dqn qnet backward: clamp must be finite and >= 0 (got %g)", (double)clamp);
+    EVG_ON_DEVICE(h);
+    return launched("dqn qnet backward", launch_dqn_qnet_backward(*net, (long long)rows, x, q, gq, *grads, static_cast<float*>(workspace), clamp, stream));
+} catch (...) { return on_exception(); }
+#endif
+
 #ifdef EVG_LEARN    // include/evg_learn.h; libevg_learn.so only
 static int learn_pointer(const char* what, const char* name, const void* p, bool required) {
     if (!p) return required ? fail(EVG_ERR_INVALID, "%s: %s is NULL", what, name) : EVG_OK;

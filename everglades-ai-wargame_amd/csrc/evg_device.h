@@ -44,6 +44,9 @@
 #ifdef EVG_DQN
 #include "../../include/evg_dqn.h"
 #endif
+#ifdef EVG_DQN_GRAD
+#include "../../include/evg_dqn_grad.h"
+#endif
 #include "evg_rng.h"
 
 namespace evg {
@@ -311,6 +314,12 @@ int launch_dqn_qnet(const evg_dqn_net& net, long long rows, const void* x, int o
                     void* stream);
 int launch_dqn_actions(const DevState& S, const float* q, int32_t* actions, void* stream, const SmartExplore* explore /* NULL: filter_actions only */,
                        uint8_t* explored /* device [N] or NULL */);
+#endif
+#ifdef EVG_DQN_GRAD
+// the backward pass of that network (dqn_grad_kernels.inc, libevg_dqngrad.so, with EVG_DQN); validated by the caller.  workspace: at least
+// EVG_DQN_GRAD_WORKSPACE_BYTES(rows, net.h1) bytes
+int launch_dqn_qnet_backward(const evg_dqn_net& net, long long rows, const float* x, const float* q, const float* gq, const evg_dqn_grads& out,
+                             float* workspace, float clamp, void* stream);
 #endif
 // self-royale (population_kernels.inc); `pop` and the sizes are validated by the caller (evg_abi.hip)
 int launch_population_clear(const DevState& S, const evg_population& pop, void* stream);

@@ -102,6 +102,9 @@ namespace evg {
 #include "dqn_decode.inc"           // the agents/DQN family's decode of its 132-way head (filter_actions) and its exploring draws
 #include "dqn_kernels.inc"          // ... and its 105 -> h1 <= 528 -> 132 network, the hidden layer streamed in chunks, on v_mfma_f32_16x16x4_f32
 #endif
+#ifdef EVG_DQN_GRAD              // `make dqngrad` (libevg_dqngrad.so, with EVG_DQN): ... plus ...
+#include "dqn_grad_kernels.inc"     // that network's backward pass: the row-parallel delta kernel and the tile-parallel weight-gradient GEMMs
+#endif
 
 // ---------------------------------------------------------------------------------------------
 // launchers

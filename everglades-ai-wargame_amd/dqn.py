@@ -4,13 +4,15 @@
                                                          # Linear(h, 132)[, ReLU]), or a 4-tuple (w1, b1, w2, b2) with final_relu=...; h in 1..528
     q = qnet(obs_seat)                                   # the env's observation tensors: [N, 105], or [N, 2, 105] with seat=p -> [N, 132]
     q = qnet.rows(x)                                     # float32 [rows, 105] -> [rows, 132]: a target network's batch
+    q = qnet.with_grad(x)                                # ... carrying autograd: loss(q.gather(1, a), y).backward() fills the parameters' .grad
     rows = env.dqn_get_action(q, eps, seat=0)            # epsilon_greedy: int32 [N, 7, 2] {unit, node 0..10}, what step_vs() takes as `actions`
     rows = env.dqn_actions(q)                            # filter_actions alone
 
 DqnQNet is SmartQNet's contract for the 105-h-132 network: the fp32 parameters are read in place on every call (optimizer.step() and load_state_dict take
 effect without rebinding), every pre-activation is the fmaf chain b[j], then k ascending (include/evg_dqn.h), the output is a plain tensor without
 autograd, there is no host synchronisation, and nothing is allocated after the first call of a shape (or at all when `out` is given).  The observation
-forms read the env's own dtype (float32, float64, int16) and convert on load as obs.float() does.
+forms read the env's own dtype (float32, float64, int16) and convert on load as obs.float() does.  with_grad(x) is optimize_model's policy forward:
+rows(x)'s values bit for bit, whose backward() is the device's backward pass (include/evg_dqn_grad.h, libevg_dqngrad.so).
 """
 import ctypes as C
 
@@ -148,6 +150,85 @@ class DqnQNet(object):
             raise ValueError("x must be a float32 tensor [rows, 105]")
         self.env._user(x, (x.shape[0], self.IN), torch.float32, "x")
         return self._run(_lib.DQN_ROWS, 0, x.shape[0], x, out)
+
+
+    # ---- the differentiable form (include/evg_dqn_grad.h, libevg_dqngrad.so)
+    def with_grad(self, x, clamp=None):
+        """rows(x) carrying autograd: x float32 [..., 105] -> a new tensor [..., 132], the same values bit for bit, whose backward() is the device's
+        backward pass (evg_dqn_qnet_backward: the delta kernel, the weight-gradient kernel and, past 128 rows, the slices' reduction) and leaves the
+        gradients of the network's parameters -- the tensors the module holds at this call -- in their .grad, as a torch forward would; x gets none.
+        `clamp` (None, or c > 0) clamps every element of the gradients this call contributes to [-c, c].  At most 65 536 rows."""
+        torch = _torch()
+        if not isinstance(x, torch.Tensor) or x.dim() < 1 or x.shape[-1] != self.IN:
+            raise ValueError("x must be a float32 tensor [..., %d]" % self.IN)
+        if x.requires_grad:
+            raise ValueError("with_grad() has no gradient with respect to x: x must not require grad")
+        if isinstance(clamp, bool) or (clamp is not None and not (isinstance(clamp, (int, float)) and 0.0 < float(clamp) < float("inf"))):
+            raise ValueError("clamp must be None or a finite number > 0 (got %r)" % (clamp,))
+        self.env._user(x, tuple(x.shape), torch.float32, "x")
+        rows = x.numel() // self.IN
+        if not 1 <= rows <= _lib.DQN_GRAD_MAX_ROWS:
+            raise ValueError("with_grad() takes 1..%d rows (got %d)" % (_lib.DQN_GRAD_MAX_ROWS, rows))
+        if x.data_ptr() % 16:
+            raise ValueError("the input must be 16-byte aligned")
+        return _grad_function()(self, 0.0 if clamp is None else float(clamp), x, *self._params())
+
+    def _backward(self, x, q, ts, gq, clamp):
+        """the gradients of ts (the parameters saved by with_grad's forward) for the upstream gradient gq [..., 132]: new tensors of their shapes"""
+        torch = _torch()
+        G = _lib.load_dqn_grad()
+        rows = x.numel() // self.IN
+        gq = gq.to(torch.float32).contiguous()
+        self.env._user(gq, tuple(x.shape[:-1]) + (self.OUT,), torch.float32, "the upstream gradient")
+        if not hasattr(self, "_grad_ws"):
+            self._grad_ws = {}
+        ws = self._grad_ws.get(rows)
+        if ws is None:                                                  # by rows, kept per row count
+            ws = self._grad_ws[rows] = torch.empty(_lib.dqn_grad_workspace_bytes(rows, self.h1) // 4, dtype=torch.float32, device=self.env.device)
+        d = _lib.EvgDqnNet()
+        d.struct_size = C.sizeof(d)
+        d.w1, d.b1, d.w2, d.b2 = (t.data_ptr() for t in ts)
+        d.h1, d.final_relu, d.reserved = self.h1, int(self.final_relu), 0
+        grads = [torch.empty_like(t, memory_format=torch.contiguous_format) for t in ts]
+        gs = _lib.EvgDqnGrads()
+        gs.struct_size = C.sizeof(gs)
+        gs.w1, gs.b1, gs.w2, gs.b2 = (g.data_ptr() for g in grads)
+        rc = G.evg_dqn_qnet_backward(self.env._h, C.byref(d), rows, C.c_void_p(x.data_ptr()), C.c_void_p(q.data_ptr()), C.c_void_p(gq.data_ptr()),
+                                     C.byref(gs), C.c_void_p(ws.data_ptr()), ws.numel() * 4, clamp, self.env._stream())
+        if rc:
+            _lib.check(rc, G)
+        return grads
+
+
+_GRAD_FN = []
+
+
+def _grad_function():
+    """the torch.autograd.Function behind with_grad (made on first use: importing this module does not import torch)"""
+    if _GRAD_FN:
+        return _GRAD_FN[0]
+    torch = _torch()
+    from torch.autograd.function import once_differentiable
+
+    class DqnQNetWithGrad(torch.autograd.Function):
+        @staticmethod
+        def forward(ctx, net, clamp, x, *params):
+            ctx.net, ctx.clamp = net, clamp
+            rows = x.numel() // net.IN
+            q = torch.empty((rows, net.OUT), dtype=torch.float32, device=x.device)      # the call's own tensor: the backward reads its signs
+            net.rows(x.reshape(rows, net.IN), out=q)
+            q = q.reshape(tuple(x.shape[:-1]) + (net.OUT,))
+            ctx.save_for_backward(x, q, *params)
+            return q
+
+        @staticmethod
+        @once_differentiable
+        def backward(ctx, gq):
+            x, q, params = ctx.saved_tensors[0], ctx.saved_tensors[1], ctx.saved_tensors[2:]
+            return (None, None, None) + tuple(ctx.net._backward(x, q, params, gq, ctx.clamp))
+
+    _GRAD_FN.append(DqnQNetWithGrad.apply)
+    return _GRAD_FN[0]
 
 
 def _head_args(env, q, out, explored):
