@@ -1423,6 +1423,63 @@ int evg_dqn_qnet_backward(evg_handle* h, const evg_dqn_net* net, int64_t rows, c
 } catch (...) { return on_exception(); }
 #endif
 
+#ifdef EVG_DQN_LEARN    // include/evg_dqn_learn.h; libevg_dqnlearn.so only
+static int dqn_learn_pointer(const char* what, const char* name, const void* p, bool required) {
+    if (!p) return required ? fail(EVG_ERR_INVALID, "%s: %s is NULL", what, name) : EVG_OK;
+    if (misaligned16(p)) return fail(EVG_ERR_INVALID, "%s: %s must be 16-byte aligned (got %p)", what, name, p);
+    return EVG_OK;
+}
+
+int evg_dqn_td_head(evg_handle* h, const evg_dqn_td_head_args* a, void* stream) try {
+    if (!h || !a) return fail(EVG_ERR_INVALID, "null handle or DQN TD head descriptor");
+    if (a->struct_size != sizeof(evg_dqn_td_head_args))
+        return fail(EVG_ERR_INVALID, "dqn td head: struct_size %u != sizeof(evg_dqn_td_head_args) %zu", a->struct_size, sizeof(evg_dqn_td_head_args));
+    if (a->batch < 1 || a->batch > EVG_DQN_TD_MAX_BATCH)
+        return fail(EVG_ERR_INVALID, "dqn td head: batch must lie in 1..%d (got %d)", EVG_DQN_TD_MAX_BATCH, a->batch);
+    if (a->mode != EVG_DQN_TD_HUBER && a->mode != EVG_DQN_TD_SQUARED) return fail(EVG_ERR_INVALID, "dqn td head: unknown mode %d", a->mode);
+    if (!std::isfinite(a->gamma)) return fail(EVG_ERR_INVALID, "dqn td head: gamma must be finite (got %g)", (double)a->gamma);
+    const struct { const char* name; const void* p; bool required; } ptrs[] = {
+        {"q_pred", a->q_pred, true}, {"action", a->action, true}, {"q_next", a->q_next, true}, {"reward", a->reward, true},
+        {"not_done", a->not_done, false}, {"weights", a->weights, false}, {"gq", a->gq, true}, {"loss", a->loss, true},
+        {"priorities", a->priorities, false}, {"estimated", a->estimated, false}, {"workspace", a->workspace, true}};
+    for (const auto& p : ptrs) {
+        const int rc = dqn_learn_pointer("dqn td head", p.name, p.p, p.required);
+        if (rc) return rc;
+    }
+    if (a->workspace_bytes < EVG_DQN_TD_WORKSPACE_BYTES)
+        return fail(EVG_ERR_INVALID, "dqn td head: the workspace is too small (%lld bytes, need %lld)", (long long)a->workspace_bytes,
+                    (long long)EVG_DQN_TD_WORKSPACE_BYTES);
+    EVG_ON_DEVICE(h);
+    return launched("dqn td head", launch_dqn_td_head(*a, stream));
+} catch (...) { return on_exception(); }
+
+// evg_adam_step's checks, word for word
+int evg_adam_step_wide(evg_handle* h, const evg_adam_args* a, void* stream) try {
+    if (!h || !a) return fail(EVG_ERR_INVALID, "null handle or Adam descriptor");
+    if (a->struct_size != sizeof(evg_adam_args))
+        return fail(EVG_ERR_INVALID, "adam: struct_size %u != sizeof(evg_adam_args) %zu", a->struct_size, sizeof(evg_adam_args));
+    if (a->n < 1 || a->n > EVG_ADAM_MAX_TENSORS) return fail(EVG_ERR_INVALID, "adam: n must lie in 1..%d (got %d)", EVG_ADAM_MAX_TENSORS, a->n);
+    if (!std::isfinite(a->lr)) return fail(EVG_ERR_INVALID, "adam: lr must be finite (got %g)", (double)a->lr);
+    if (!(a->beta1 >= 0.0f && a->beta1 < 1.0f) || !(a->beta2 >= 0.0f && a->beta2 < 1.0f))
+        return fail(EVG_ERR_INVALID, "adam: the betas must lie in [0, 1) (got %g, %g)", (double)a->beta1, (double)a->beta2);
+    if (!(a->eps > 0.0f) || !std::isfinite(a->eps)) return fail(EVG_ERR_INVALID, "adam: eps must be finite and > 0 (got %g)", (double)a->eps);
+    if (!(a->clamp >= 0.0f) || !std::isfinite(a->clamp)) return fail(EVG_ERR_INVALID, "adam: clamp must be finite and >= 0 (got %g)", (double)a->clamp);
+    { const int rc = dqn_learn_pointer("adam", "ctl", a->ctl, true); if (rc) return rc; }
+    for (int i = 0; i < a->n; ++i) {
+        const evg_adam_tensor& t = a->t[i];
+        if (t.count < 1 || t.count > EVG_ADAM_MAX_COUNT)
+            return fail(EVG_ERR_INVALID, "adam: tensor %d: count must lie in 1..%d (got %lld)", i, EVG_ADAM_MAX_COUNT, (long long)t.count);
+        const struct { const char* name; const void* p; } ptrs[] = {{"param", t.param}, {"grad", t.grad}, {"m", t.m}, {"v", t.v}};
+        for (const auto& p : ptrs) {
+            if (!p.p) return fail(EVG_ERR_INVALID, "adam: tensor %d: %s is NULL", i, p.name);
+            if (misaligned16(p.p)) return fail(EVG_ERR_INVALID, "adam: tensor %d: %s must be 16-byte aligned (got %p)", i, p.name, p.p);
+        }
+    }
+    EVG_ON_DEVICE(h);
+    return launched("adam", launch_adam_step_wide(*a, stream));
+} catch (...) { return on_exception(); }
+#endif
+
 #ifdef EVG_LEARN    // include/evg_learn.h; libevg_learn.so only
 static int learn_pointer(const char* what, const char* name, const void* p, bool required) {
     if (!p) return required ? fail(EVG_ERR_INVALID, "%s: %s is NULL", what, name) : EVG_OK;

@@ -47,6 +47,9 @@
 #ifdef EVG_DQN_GRAD
 #include "../../include/evg_dqn_grad.h"
 #endif
+#ifdef EVG_DQN_LEARN
+#include "../../include/evg_dqn_learn.h"
+#endif
 #include "evg_rng.h"
 
 namespace evg {
@@ -320,6 +323,11 @@ int launch_dqn_actions(const DevState& S, const float* q, int32_t* actions, void
 // EVG_DQN_GRAD_WORKSPACE_BYTES(rows, net.h1) bytes
 int launch_dqn_qnet_backward(const evg_dqn_net& net, long long rows, const float* x, const float* q, const float* gq, const evg_dqn_grads& out,
                              float* workspace, float clamp, void* stream);
+#endif
+#ifdef EVG_DQN_LEARN
+// the rest of that family's learner step (dqn_learn_kernels.inc, libevg_dqnlearn.so, with EVG_DQN and EVG_DQN_GRAD); validated by the caller
+int launch_dqn_td_head(const evg_dqn_td_head_args& a, void* stream);
+int launch_adam_step_wide(const evg_adam_args& a, void* stream);
 #endif
 // self-royale (population_kernels.inc); `pop` and the sizes are validated by the caller (evg_abi.hip)
 int launch_population_clear(const DevState& S, const evg_population& pop, void* stream);

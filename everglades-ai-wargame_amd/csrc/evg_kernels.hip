@@ -105,6 +105,9 @@ namespace evg {
 #ifdef EVG_DQN_GRAD              // `make dqngrad` (libevg_dqngrad.so, with EVG_DQN): ... plus ...
 #include "dqn_grad_kernels.inc"     // that network's backward pass: the row-parallel delta kernel and the tile-parallel weight-gradient GEMMs
 #endif
+#ifdef EVG_DQN_LEARN             // `make dqnlearn` (libevg_dqnlearn.so, with EVG_DQN and EVG_DQN_GRAD): ... plus ...
+#include "dqn_learn_kernels.inc"    // the rest of that family's optimize_model: the top-7 TD head and Adam over a large network launched over a grid
+#endif
 
 // ---------------------------------------------------------------------------------------------
 // launchers

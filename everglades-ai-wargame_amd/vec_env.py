@@ -615,6 +615,14 @@ class EvergladesVecEnv(object):
         from . import dqn
         return dqn.get_action(self, q, epsilon, seat=seat, out=out, explored=explored)
 
+    def dqn_learner(self, policy, target, **kw):
+        """optimize_model for the agents/DQN family on this env's device (everglades_amd.DqnFamilyLearner; include/evg_dqn_learn.h): `policy` and
+        `target` as dqn_qnet() takes them.  Keywords: lr=1e-4, gamma=0.99, mode="huber" | "squared", clamp=1.0 (None: no clamp), fresh_state=False,
+        betas=(0.9, 0.999), eps=1e-8, final_relu=None.  learner.step_on((state, action [B, 7], next_state, reward, not_done or None)) is one training
+        step without a torch op; mode="squared" with clamp=None is prioritized_optimize_model."""
+        from .dqn_learner import DqnFamilyLearner
+        return DqnFamilyLearner(self, policy, target, **kw)
+
     def q_population(self, team0, team1=None, final_relu=None, max_rows=None, precision="fp32"):
         """Self-royale (everglades_amd.QPopulation; evg_population): two teams of Minimized Q networks, a member per env and seat drawn each episode --
         `pop(shared, swarm)` -> the q [N, 2, 12, 11] step_q() takes, `pop.end_of_turn()` behind the step.  team1=None plays team0 on both seats.

@@ -8,9 +8,11 @@ and ring of raw observations, plus DQNAgent.optimize_model (DQNAgent.py:218-282)
     loss = F.smooth_l1_loss(state_action_values, expected); loss.backward(); param.grad.data.clamp_(-1, 1); Adam; the target update
 
 -- with the policy forward either torch's own (the default) or, with --device-backward, DqnQNet.with_grad: the same values from one launch, whose
-backward() is the device's backward pass (include/evg_dqn_grad.h).  The TD head and Adam of this family are torch's in both.
+backward() is the device's backward pass (include/evg_dqn_grad.h).  The TD head and Adam of this family are torch's in both.  With --device-learner
+the whole torch block is one learner.step_on(batch) of env.dqn_learner (include/evg_dqn_learn.h): both forwards, the top-7 TD head, the backward and
+Adam as a chain of launches; the ring and the index draw stay torch's.
 
-    python examples/dqn_training.py [envs] [turns] [batch] [--device-backward]
+    python examples/dqn_training.py [envs] [turns] [batch] [--device-backward | --device-learner]
 """
 import math
 import os
@@ -30,7 +32,7 @@ def make_net(dev):
     return torch.nn.Sequential(torch.nn.Linear(105, 528), torch.nn.ReLU(), torch.nn.Linear(528, 132), torch.nn.ReLU()).to(dev)     # QNetwork.forward
 
 
-def main(envs=4096, turns=300, batch=128, device_backward=False, opponent="random_actions", ring=8):
+def main(envs=4096, turns=300, batch=128, device_backward=False, opponent="random_actions", ring=8, device_learner=False):
     env = evg.EvergladesVecEnv(envs, seed=1, auto_reset=True)
     env.reset()
     dev = env.device
@@ -39,6 +41,7 @@ def main(envs=4096, turns=300, batch=128, device_backward=False, opponent="rando
     target.load_state_dict(policy.state_dict())
     optimizer = torch.optim.Adam(policy.parameters(), lr=LR)
     qnet, tnet = env.dqn_qnet(policy), env.dqn_qnet(target)
+    learner = env.dqn_learner(policy, target, lr=LR, gamma=GAMMA, mode="huber", clamp=1.0) if device_learner else None
     explored = torch.zeros(envs, dtype=torch.uint8, device=dev)
     mem = dict(state=torch.zeros((ring, envs, 105), device=dev), action=torch.zeros((ring, envs, 7), dtype=torch.int64, device=dev),
                reward=torch.zeros((ring, envs), device=dev), next_state=torch.zeros((ring, envs, 105), device=dev))
@@ -62,24 +65,30 @@ def main(envs=4096, turns=300, batch=128, device_backward=False, opponent="rando
         idx = torch.randint(0, filled, (batch,), generator=gen, device=dev)
         state, action = mem["state"].view(-1, 105)[idx], mem["action"].view(-1, 7)[idx]
         rew, nxt = mem["reward"].view(-1)[idx], mem["next_state"].view(-1, 105)[idx]
-        q = qnet.with_grad(state) if device_backward else policy(state)
-        predicted = q.gather(1, action)
-        expected = tnet.rows(nxt).topk(7, 1)[0] * GAMMA + rew.unsqueeze(1).repeat(1, 7)
-        loss = F.smooth_l1_loss(predicted, expected)
-        optimizer.zero_grad()
-        loss.backward()
-        for p in policy.parameters():
-            p.grad.data.clamp_(-1, 1)
-        optimizer.step()
+        if learner is not None:
+            loss = learner.step_on((state, action, nxt, rew, None))
+        else:
+            q = qnet.with_grad(state) if device_backward else policy(state)
+            predicted = q.gather(1, action)
+            expected = tnet.rows(nxt).topk(7, 1)[0] * GAMMA + rew.unsqueeze(1).repeat(1, 7)
+            loss = F.smooth_l1_loss(predicted, expected)
+            optimizer.zero_grad()
+            loss.backward()
+            for p in policy.parameters():
+                p.grad.data.clamp_(-1, 1)
+            optimizer.step()
         if t % TARGET_UPDATE == TARGET_UPDATE - 1:
-            target.load_state_dict(policy.state_dict())
+            if learner is not None:
+                learner.sync_target()
+            else:
+                target.load_state_dict(policy.state_dict())
         if t % 20 == 19:                                           # the only host reads of the loop
             losses.append(float(loss))
     torch.cuda.synchronize()
     dt = time.perf_counter() - t0
     finite = all(bool(torch.isfinite(p).all()) for p in policy.parameters()) and all(math.isfinite(v) for v in losses)
     print("%d envs x %d turns of the agents/DQN training loop against %s, batch %d, %s: %.1f us per turn, loss %s, all finite: %s" % (
-        envs, turns, opponent, batch, "device backward (DqnQNet.with_grad)" if device_backward else "torch backward", dt / turns * 1e6,
+        envs, turns, opponent, batch, "device learner (DqnFamilyLearner.step_on)" if device_learner else "device backward (DqnQNet.with_grad)" if device_backward else "torch backward", dt / turns * 1e6,
         " ".join("%.4f" % v for v in losses), finite))
     env.close()
     return finite
@@ -88,7 +97,10 @@ def main(envs=4096, turns=300, batch=128, device_backward=False, opponent="rando
 if __name__ == "__main__":
     flags = [a for a in sys.argv[1:] if a.startswith("--")]
     a = [v for v in sys.argv[1:] if not v.startswith("--")]
-    if set(flags) - {"--device-backward"}:
-        sys.exit("unknown option %s" % " ".join(sorted(set(flags) - {"--device-backward"})))
-    ok = main(int(a[0]) if len(a) > 0 else 4096, int(a[1]) if len(a) > 1 else 300, int(a[2]) if len(a) > 2 else 128, "--device-backward" in flags)
+    if set(flags) - {"--device-backward", "--device-learner"}:
+        sys.exit("unknown option %s" % " ".join(sorted(set(flags) - {"--device-backward", "--device-learner"})))
+    if len(flags) > 1:
+        sys.exit("--device-backward and --device-learner exclude each other")
+    ok = main(int(a[0]) if len(a) > 0 else 4096, int(a[1]) if len(a) > 1 else 300, int(a[2]) if len(a) > 2 else 128, "--device-backward" in flags,
+              device_learner="--device-learner" in flags)
     sys.exit(0 if ok else 1)
