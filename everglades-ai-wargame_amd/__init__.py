@@ -14,6 +14,7 @@ from .qnet import MinimizedQNet, MinimizedQNetBf16, SmartQNet, SmartQNetBf16
 from .dqn import DqnQNet
 from .learner import DqnLearner
 from .dqn_learner import DqnFamilyLearner
+from .dqn_replay import DqnReplay, PrioritizedDqnReplay
 from .pop_learner import PopulationLearner
 from .league import OpponentLeague
 from .population import QPopulation, QPopulationBf16, SmartQPopulation, SmartQPopulationBf16
@@ -22,7 +23,7 @@ from .env import EvergladesEnv, canonical_actions
 from .distributed import shard_range, gather_episode_results, win_counts, ResultGather, NativeGather
 from .harness import evaluate, evaluate_all, proportion_confint_normal
 
-__all__ = ["EvergladesVecEnv", "SmartReplay", "PrioritizedSmartReplay", "SmartQNet", "MinimizedQNet", "SmartQNetBf16", "MinimizedQNetBf16", "DqnQNet", "DqnLearner", "DqnFamilyLearner", "PopulationLearner", "OpponentLeague", "QPopulation", "SmartQPopulation", "QPopulationBf16", "SmartQPopulationBf16", "PipelinedVecEnv", "EvergladesEnv", "EvgError", "EvgFault", "load_library", "default_tables", "tables_from_json",
+__all__ = ["EvergladesVecEnv", "SmartReplay", "PrioritizedSmartReplay", "SmartQNet", "MinimizedQNet", "SmartQNetBf16", "MinimizedQNetBf16", "DqnQNet", "DqnLearner", "DqnFamilyLearner", "DqnReplay", "PrioritizedDqnReplay", "PopulationLearner", "OpponentLeague", "QPopulation", "SmartQPopulation", "QPopulationBf16", "SmartQPopulationBf16", "PipelinedVecEnv", "EvergladesEnv", "EvgError", "EvgFault", "load_library", "default_tables", "tables_from_json",
            "canonical_actions", "shard_range", "gather_episode_results", "win_counts", "ResultGather", "NativeGather", "evaluate", "evaluate_all",
            "proportion_confint_normal"]
 

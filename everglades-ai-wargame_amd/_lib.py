@@ -57,6 +57,34 @@ DQN_LEARN_EXPORTS = ["evg_dqn_td_head", "evg_adam_step_wide"]
 # include/evg_dqn_learn.h
 DQN_TD_MODES = {"huber": 0, "squared": 1}
 DQN_TD_ACTIONS, DQN_TD_MAX_BATCH, DQN_TD_MAX_BLOCKS, DQN_TD_WORKSPACE_BYTES, ADAM_WIDE_MAX_BLOCKS = 7, 1 << 20, 1024, 4096, 512
+# `make -C csrc dqnreplay`: libevg_dqnlearn.so plus the five entry points of include/evg_dqn_replay.h (DqnReplay loads it: load_dqn_replay)
+DQN_REPLAY_LIB_PATH = os.path.join(HERE, "libevg_dqnreplay.so")
+DQN_REPLAY_EXPORTS = ["evg_dqn_replay_clear", "evg_dqn_replay_record", "evg_dqn_replay_size", "evg_dqn_replay_sample", "evg_dqn_replay_gather",
+                      "evg_dqn_replay_priority_clear", "evg_dqn_replay_update_priorities", "evg_dqn_replay_sample_prioritized"]
+# EVG_DQN_REPLAY_MAX_BATCH, _TILE, _GATHER_MAX_BLOCKS, _DRAW_MAX_BLOCKS, _S_BAD_ACTION, _TERMINAL_NEXT of include/evg_dqn_replay.h
+DQN_REPLAY_MAX_BATCH, DQN_REPLAY_TILE, DQN_REPLAY_GATHER_MAX_BLOCKS, DQN_REPLAY_DRAW_MAX_BLOCKS = 1 << 20, 16, 2048, 256
+DQN_REPLAY_S_BAD_ACTION, DQN_REPLAY_TERMINAL_NEXT = 8, 1
+DQN_REPLAY_S_BAD_PRIORITY = 4                       # EVG_DQN_REPLAY_S_BAD_PRIORITY (= REPLAY_S_BAD_PRIORITY)
+
+
+def dqn_replay_obs_stride(N, elem):
+    """EVG_DQN_REPLAY_OBS_STRIDE: bytes from one slot's observations to the next (padded to 16)"""
+    return (N * 105 * elem + 15) // 16 * 16
+
+
+def dqn_replay_act_stride(N):
+    """EVG_DQN_REPLAY_ACT_STRIDE: ints from one slot's order rows to the next"""
+    return (N * 14 + 3) // 4 * 4
+
+
+def dqn_replay_scan_ints(slots, N):
+    """EVG_DQN_REPLAY_SCAN_INTS"""
+    return (slots * N + 3) // 4 + (slots * N + 1023) // 1024
+
+
+def dqn_replay_pscan_words(slots, N):
+    """EVG_DQN_REPLAY_PSCAN_WORDS"""
+    return (slots * N + 3) // 4 + 2 * ((slots * N + 1023) // 1024)
 
 
 def dqn_grad_slices(rows):
@@ -162,6 +190,22 @@ class EvgReplay(C.Structure):
         ("shared", C.c_void_p), ("swarm", C.c_void_p), ("directions", C.c_void_p), ("reward", C.c_void_p), ("meta", C.c_void_p),
         ("count", C.c_void_p), ("env_state", C.c_void_p), ("gamma_pow", C.c_void_p), ("scan", C.c_void_p), ("ctl", C.c_void_p),
     ]
+
+
+class EvgDqnReplay(C.Structure):
+    """evg_dqn_replay of include/evg_dqn_replay.h: the descriptor of the agents/DQN family's replay memory (device pointers the caller owns)."""
+    _fields_ = [
+        ("struct_size", C.c_uint32), ("slots", C.c_int32), ("seat", C.c_int32), ("shaping", C.c_int32), ("shaping_from", C.c_int32),
+        ("shaping_to", C.c_int32), ("transition_episodes", C.c_int32), ("reserved", C.c_int32), ("episode_base", C.c_int64),
+        ("obs", C.c_void_p), ("actions", C.c_void_p), ("reward", C.c_void_p), ("meta", C.c_void_p), ("valid", C.c_void_p),
+        ("env_state", C.c_void_p), ("scan", C.c_void_p), ("ctl", C.c_void_p),
+    ]
+
+
+class EvgDqnReplayPriority(C.Structure):
+    """evg_dqn_replay_priority of include/evg_dqn_replay.h: the weights, stamps and work space of prioritized sampling (device pointers)."""
+    _fields_ = [("struct_size", C.c_uint32), ("alpha", C.c_float), ("weight", C.c_void_p), ("stamp", C.c_void_p), ("pscan", C.c_void_p),
+                ("pctl", C.c_void_p)]
 
 
 class EvgReplayPriority(C.Structure):
@@ -413,6 +457,17 @@ def load(path=None):
     if hasattr(L, "evg_dqn_td_head"):                # libevg_dqnlearn.so only
         L.evg_dqn_td_head.argtypes = [vp, C.POINTER(EvgDqnTdHeadArgs), vp]
         L.evg_adam_step_wide.argtypes = [vp, C.POINTER(EvgAdamArgs), vp]
+    if hasattr(L, "evg_dqn_replay_clear"):           # libevg_dqnreplay.so only
+        dr = C.POINTER(EvgDqnReplay)
+        L.evg_dqn_replay_clear.argtypes = [vp, dr, vp]
+        L.evg_dqn_replay_record.argtypes = [vp, dr, C.c_int64, vp, vp, vp, vp]
+        L.evg_dqn_replay_size.argtypes = [vp, dr, vp]
+        L.evg_dqn_replay_sample.argtypes = [vp, dr, C.c_int, C.c_uint64, C.c_int, vp, vp, vp, vp, vp, vp, vp]
+        L.evg_dqn_replay_gather.argtypes = [vp, dr, C.c_int, vp, C.c_int, vp, vp, vp, vp, vp, vp]
+        dp = C.POINTER(EvgDqnReplayPriority)
+        L.evg_dqn_replay_priority_clear.argtypes = [vp, dr, dp, vp]
+        L.evg_dqn_replay_update_priorities.argtypes = [vp, dr, dp, C.c_int, vp, vp, vp]
+        L.evg_dqn_replay_sample_prioritized.argtypes = [vp, dr, dp, C.c_int, C.c_uint64, C.c_int, C.c_float, vp, vp, vp, vp, vp, vp, vp, vp]
     lp = C.POINTER(EvgLeague)
     L.evg_league_clear.argtypes = [vp, lp, vp]
     L.evg_league_assign.argtypes = [vp, lp, vp, vp]
@@ -532,6 +587,17 @@ def load_dqn_learn():
     missing = [n for n in DQN_EXPORTS + DQN_GRAD_EXPORTS + DQN_LEARN_EXPORTS if not hasattr(L, n)]
     if missing:
         raise EvgError("%s does not export %s; rebuild it (make -C everglades-ai-wargame_amd/csrc dqnlearn)" % (DQN_LEARN_LIB_PATH, ", ".join(missing)))
+    return L
+
+
+def load_dqn_replay():
+    """Load libevg_dqnreplay.so: libevg.so's sources built with -DEVG_DQN -DEVG_DQN_GRAD -DEVG_DQN_LEARN -DEVG_DQN_REPLAY, which exports what
+    libevg_dqnlearn.so does plus DQN_REPLAY_EXPORTS (include/evg_dqn_replay.h).  A handle of libevg.so is valid in it; a failed call's text is its own
+    evg_last_error."""
+    L = load(DQN_REPLAY_LIB_PATH)
+    missing = [n for n in DQN_EXPORTS + DQN_GRAD_EXPORTS + DQN_LEARN_EXPORTS + DQN_REPLAY_EXPORTS if not hasattr(L, n)]
+    if missing:
+        raise EvgError("%s does not export %s; rebuild it (make -C everglades-ai-wargame_amd/csrc dqnreplay)" % (DQN_REPLAY_LIB_PATH, ", ".join(missing)))
     return L
 
 

@@ -1480,6 +1480,150 @@ int evg_adam_step_wide(evg_handle* h, const evg_adam_args* a, void* stream) try 
 } catch (...) { return on_exception(); }
 #endif
 
+#ifdef EVG_DQN_REPLAY    // include/evg_dqn_replay.h; libevg_dqnreplay.so only
+// everything decided on the descriptor alone comes first: those refusals need no device and read nothing of the handle
+static int check_dqn_replay(const evg_handle* h, const evg_dqn_replay* m) {
+    if (!h || !m) return fail(EVG_ERR_INVALID, "null handle or DQN replay descriptor");
+    if (m->struct_size != sizeof(evg_dqn_replay))
+        return fail(EVG_ERR_INVALID, "dqn replay: struct_size %u != sizeof(evg_dqn_replay) %zu", m->struct_size, sizeof(evg_dqn_replay));
+    if (m->slots < 2) return fail(EVG_ERR_INVALID, "dqn replay: slots must be >= 2 (got %d)", m->slots);
+    if (m->seat < 0 || m->seat > 1) return fail(EVG_ERR_INVALID, "dqn replay: seat must be 0 or 1 (got %d)", m->seat);
+    if (m->shaping < EVG_SHAPE_NORMALIZED_SCORE || m->shaping > EVG_SHAPE_CUSTOM) return fail(EVG_ERR_INVALID, "dqn replay: unknown shaping %d", m->shaping);
+    if (m->shaping == EVG_SHAPE_TRANSITION) {
+        if (m->shaping_from < EVG_SHAPE_NORMALIZED_SCORE || m->shaping_from > EVG_SHAPE_REWARD_SHORT_GAMES || m->shaping_to < EVG_SHAPE_NORMALIZED_SCORE ||
+            m->shaping_to > EVG_SHAPE_REWARD_SHORT_GAMES)
+            return fail(EVG_ERR_INVALID, "dqn replay: transition shaping needs two base functions (got %d, %d)", m->shaping_from, m->shaping_to);
+        if (m->transition_episodes < 1) return fail(EVG_ERR_INVALID, "dqn replay: transition_episodes must be >= 1");
+    }
+    const struct { const char* name; const void* p; } ptrs[] = {{"obs", m->obs}, {"actions", m->actions}, {"reward", m->reward}, {"meta", m->meta},
+                                                                 {"valid", m->valid}, {"env_state", m->env_state}, {"scan", m->scan}, {"ctl", m->ctl}};
+    for (const auto& p : ptrs) {
+        if (!p.p) return fail(EVG_ERR_INVALID, "dqn replay: the descriptor's %s is NULL", p.name);
+        if (misaligned16(p.p)) return fail(EVG_ERR_INVALID, "dqn replay: the descriptor's %s must be 16-byte aligned (got %p)", p.name, p.p);
+    }
+    return EVG_OK;
+}
+
+static int check_dqn_replay_batch(int batch, int flags, const float* state, const int64_t* action, const float* next_state, const float* reward,
+                                  const uint8_t* not_done, const int32_t* handles) {
+    if (batch < 1 || batch > EVG_DQN_REPLAY_MAX_BATCH)
+        return fail(EVG_ERR_INVALID, "dqn replay: batch must lie in 1..%d (got %d)", EVG_DQN_REPLAY_MAX_BATCH, batch);
+    if (flags & ~EVG_DQN_REPLAY_TERMINAL_NEXT) return fail(EVG_ERR_INVALID, "dqn replay: unknown flags %d", flags);
+    const struct { const char* name; const void* p; } ptrs[] = {{"state", state}, {"action", action}, {"next_state", next_state}, {"reward", reward},
+                                                                 {"not_done", not_done}, {"handles", handles}};
+    for (const auto& p : ptrs) {
+        if (!p.p) return fail(EVG_ERR_INVALID, "dqn replay: %s is NULL", p.name);
+        if (misaligned16(p.p)) return fail(EVG_ERR_INVALID, "dqn replay: %s must be 16-byte aligned (got %p)", p.name, p.p);
+    }
+    return EVG_OK;
+}
+
+// what needs the handle: the ring's size, and the flag that only a handle without auto_reset can honour
+static int check_dqn_replay_handle(const evg_handle* h, const evg_dqn_replay* m, int flags) {
+    if ((long long)m->slots * h->S.N > 0x7FFFFFFFLL / 8) return fail(EVG_ERR_INVALID, "dqn replay: slots x N too large");
+    if ((flags & EVG_DQN_REPLAY_TERMINAL_NEXT) && h->S.auto_reset)
+        return fail(EVG_ERR_INVALID, "dqn replay: EVG_DQN_REPLAY_TERMINAL_NEXT on an auto_reset handle (the slot behind a finishing step holds the next "
+                                     "episode's first observation, not the terminal one)");
+    return EVG_OK;
+}
+
+int evg_dqn_replay_clear(evg_handle* h, const evg_dqn_replay* m, void* stream) try {
+    { const int rc = check_dqn_replay(h, m); if (rc) return rc; }
+    { const int rc = check_dqn_replay_handle(h, m, 0); if (rc) return rc; }
+    EVG_ON_DEVICE(h);
+    return launched("dqn replay clear", launch_dqn_replay_clear(h->S, *m, stream));
+} catch (...) { return on_exception(); }
+
+int evg_dqn_replay_record(evg_handle* h, const evg_dqn_replay* m, int64_t turn, const float* reward_in, const uint8_t* done_in, const float* custom_in,
+                          void* stream) try {
+    { const int rc = check_dqn_replay(h, m); if (rc) return rc; }
+    if (turn < 0) return fail(EVG_ERR_INVALID, "dqn replay record: turn must be >= 0");
+    if (!done_in || (m->shaping == EVG_SHAPE_CUSTOM ? !custom_in : !reward_in))
+        return fail(EVG_ERR_INVALID, "dqn replay record: done_in and %s are required", m->shaping == EVG_SHAPE_CUSTOM ? "custom_in" : "reward_in");
+    EVG_NEED_ALIGNED8(reward_in);
+    { const int rc = check_dqn_replay_handle(h, m, 0); if (rc) return rc; }
+    EVG_ON_DEVICE(h);
+    return launched("dqn replay record", launch_dqn_replay_record(h->S, *m, (long long)turn, reward_in, done_in, custom_in, stream));
+} catch (...) { return on_exception(); }
+
+int evg_dqn_replay_size(evg_handle* h, const evg_dqn_replay* m, void* stream) try {
+    { const int rc = check_dqn_replay(h, m); if (rc) return rc; }
+    { const int rc = check_dqn_replay_handle(h, m, 0); if (rc) return rc; }
+    EVG_ON_DEVICE(h);
+    return launched("dqn replay count", launch_dqn_replay_count(h->S, *m, 0, stream));
+} catch (...) { return on_exception(); }
+
+int evg_dqn_replay_sample(evg_handle* h, const evg_dqn_replay* m, int batch, uint64_t seed, int flags, float* state, int64_t* action, float* next_state,
+                          float* reward, uint8_t* not_done, int32_t* handles, void* stream) try {
+    { const int rc = check_dqn_replay(h, m); if (rc) return rc; }
+    { const int rc = check_dqn_replay_batch(batch, flags, state, action, next_state, reward, not_done, handles); if (rc) return rc; }
+    { const int rc = check_dqn_replay_handle(h, m, flags); if (rc) return rc; }
+    EVG_ON_DEVICE(h);
+    int rc = launch_dqn_replay_count(h->S, *m, 1, stream);
+    if (!rc) rc = launch_dqn_replay_draw(h->S, *m, batch, seed, handles, stream);
+    if (!rc) rc = launch_dqn_replay_gather(h->S, *m, h->cfg.obs_dtype, batch, flags, handles, state, action, next_state, reward, not_done, stream);
+    return launched("dqn replay sample", rc);
+} catch (...) { return on_exception(); }
+
+int evg_dqn_replay_gather(evg_handle* h, const evg_dqn_replay* m, int batch, const int32_t* handles, int flags, float* state, int64_t* action,
+                          float* next_state, float* reward, uint8_t* not_done, void* stream) try {
+    { const int rc = check_dqn_replay(h, m); if (rc) return rc; }
+    { const int rc = check_dqn_replay_batch(batch, flags, state, action, next_state, reward, not_done, handles); if (rc) return rc; }
+    { const int rc = check_dqn_replay_handle(h, m, flags); if (rc) return rc; }
+    EVG_ON_DEVICE(h);
+    return launched("dqn replay gather",
+                    launch_dqn_replay_gather(h->S, *m, h->cfg.obs_dtype, batch, flags, handles, state, action, next_state, reward, not_done, stream));
+} catch (...) { return on_exception(); }
+
+static int check_dqn_replay_priority(const evg_dqn_replay_priority* p) {
+    if (!p) return fail(EVG_ERR_INVALID, "null DQN replay priority descriptor");
+    if (p->struct_size != sizeof(evg_dqn_replay_priority))
+        return fail(EVG_ERR_INVALID, "dqn replay priority: struct_size %u != sizeof(evg_dqn_replay_priority) %zu", p->struct_size,
+                    sizeof(evg_dqn_replay_priority));
+    if (!(p->alpha >= 0.0f && p->alpha <= 1.0f)) return fail(EVG_ERR_INVALID, "dqn replay priority: alpha must lie in [0, 1] (got %g)", (double)p->alpha);
+    if (!p->weight || !p->stamp || !p->pscan || !p->pctl) return fail(EVG_ERR_INVALID, "dqn replay priority: weight, stamp, pscan and pctl are required");
+    EVG_NEED_ALIGNED16(p->weight); EVG_NEED_ALIGNED16(p->stamp); EVG_NEED_ALIGNED8(p->pscan); EVG_NEED_ALIGNED8(p->pctl);
+    return EVG_OK;
+}
+
+int evg_dqn_replay_priority_clear(evg_handle* h, const evg_dqn_replay* m, const evg_dqn_replay_priority* p, void* stream) try {
+    { const int rc = check_dqn_replay(h, m); if (rc) return rc; }
+    { const int rc = check_dqn_replay_priority(p); if (rc) return rc; }
+    { const int rc = check_dqn_replay_handle(h, m, 0); if (rc) return rc; }
+    EVG_ON_DEVICE(h);
+    return launched("dqn replay priority clear", launch_dqn_replay_priority_clear(h->S, *m, *p, stream));
+} catch (...) { return on_exception(); }
+
+int evg_dqn_replay_update_priorities(evg_handle* h, const evg_dqn_replay* m, const evg_dqn_replay_priority* p, int batch, const int32_t* handles,
+                                     const float* priorities, void* stream) try {
+    { const int rc = check_dqn_replay(h, m); if (rc) return rc; }
+    { const int rc = check_dqn_replay_priority(p); if (rc) return rc; }
+    if (batch < 1 || batch > EVG_DQN_REPLAY_MAX_BATCH)
+        return fail(EVG_ERR_INVALID, "dqn replay: batch must lie in 1..%d (got %d)", EVG_DQN_REPLAY_MAX_BATCH, batch);
+    if (!handles || !priorities) return fail(EVG_ERR_INVALID, "dqn replay: handles and priorities are required");
+    EVG_NEED_ALIGNED16(handles);
+    { const int rc = check_dqn_replay_handle(h, m, 0); if (rc) return rc; }
+    EVG_ON_DEVICE(h);
+    return launched("dqn replay priority update", launch_dqn_replay_priority_update(h->S, *m, *p, batch, handles, priorities, stream));
+} catch (...) { return on_exception(); }
+
+int evg_dqn_replay_sample_prioritized(evg_handle* h, const evg_dqn_replay* m, const evg_dqn_replay_priority* p, int batch, uint64_t seed, int flags,
+                                      float beta, float* state, int64_t* action, float* next_state, float* reward, uint8_t* not_done, int32_t* handles,
+                                      float* weights_out, void* stream) try {
+    { const int rc = check_dqn_replay(h, m); if (rc) return rc; }
+    { const int rc = check_dqn_replay_priority(p); if (rc) return rc; }
+    { const int rc = check_dqn_replay_batch(batch, flags, state, action, next_state, reward, not_done, handles); if (rc) return rc; }
+    if (!(beta >= 0.0f) || beta > 3.402823466e+38f) return fail(EVG_ERR_INVALID, "dqn replay priority: beta must be finite and >= 0 (got %g)", (double)beta);
+    if (!weights_out) return fail(EVG_ERR_INVALID, "dqn replay: weights_out is NULL");
+    EVG_NEED_ALIGNED16(weights_out);
+    { const int rc = check_dqn_replay_handle(h, m, flags); if (rc) return rc; }
+    EVG_ON_DEVICE(h);
+    int rc = launch_dqn_replay_priority_draw(h->S, *m, *p, batch, seed, beta, handles, weights_out, stream);
+    if (!rc) rc = launch_dqn_replay_gather(h->S, *m, h->cfg.obs_dtype, batch, flags, handles, state, action, next_state, reward, not_done, stream);
+    return launched("dqn replay sample prioritized", rc);
+} catch (...) { return on_exception(); }
+#endif
+
 #ifdef EVG_LEARN    // include/evg_learn.h; libevg_learn.so only
 static int learn_pointer(const char* what, const char* name, const void* p, bool required) {
     if (!p) return required ? fail(EVG_ERR_INVALID, "%s: %s is NULL", what, name) : EVG_OK;

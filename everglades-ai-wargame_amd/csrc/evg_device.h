@@ -50,6 +50,9 @@
 #ifdef EVG_DQN_LEARN
 #include "../../include/evg_dqn_learn.h"
 #endif
+#ifdef EVG_DQN_REPLAY
+#include "../../include/evg_dqn_replay.h"
+#endif
 #include "evg_rng.h"
 
 namespace evg {
@@ -328,6 +331,21 @@ int launch_dqn_qnet_backward(const evg_dqn_net& net, long long rows, const float
 // the rest of that family's learner step (dqn_learn_kernels.inc, libevg_dqnlearn.so, with EVG_DQN and EVG_DQN_GRAD); validated by the caller
 int launch_dqn_td_head(const evg_dqn_td_head_args& a, void* stream);
 int launch_adam_step_wide(const evg_adam_args& a, void* stream);
+#endif
+#ifdef EVG_DQN_REPLAY
+// that family's replay memory of raw observations (dqn_replay_kernels.inc, libevg_dqnreplay.so); validated by the caller
+int launch_dqn_replay_clear(const DevState& S, const evg_dqn_replay& m, void* stream);
+int launch_dqn_replay_record(const DevState& S, const evg_dqn_replay& m, long long turn, const float* reward, const uint8_t* done, const float* custom,
+                             void* stream);
+int launch_dqn_replay_count(const DevState& S, const evg_dqn_replay& m, int count_call /* 1: a sample's count (advances the call counter) */, void* stream);
+int launch_dqn_replay_draw(const DevState& S, const evg_dqn_replay& m, int batch, uint64_t seed, int32_t* handles, void* stream);
+int launch_dqn_replay_gather(const DevState& S, const evg_dqn_replay& m, int obs_dtype, int batch, int flags, const int32_t* handles, float* state,
+                             int64_t* action, float* next_state, float* reward, uint8_t* not_done, void* stream);
+int launch_dqn_replay_priority_clear(const DevState& S, const evg_dqn_replay& m, const evg_dqn_replay_priority& p, void* stream);
+int launch_dqn_replay_priority_update(const DevState& S, const evg_dqn_replay& m, const evg_dqn_replay_priority& p, int batch, const int32_t* handles,
+                                      const float* priorities, void* stream);
+int launch_dqn_replay_priority_draw(const DevState& S, const evg_dqn_replay& m, const evg_dqn_replay_priority& p, int batch, uint64_t seed, float beta,
+                                    int32_t* handles, float* weights, void* stream);
 #endif
 // self-royale (population_kernels.inc); `pop` and the sizes are validated by the caller (evg_abi.hip)
 int launch_population_clear(const DevState& S, const evg_population& pop, void* stream);

@@ -108,6 +108,9 @@ namespace evg {
 #ifdef EVG_DQN_LEARN             // `make dqnlearn` (libevg_dqnlearn.so, with EVG_DQN and EVG_DQN_GRAD): ... plus ...
 #include "dqn_learn_kernels.inc"    // the rest of that family's optimize_model: the top-7 TD head and Adam over a large network launched over a grid
 #endif
+#ifdef EVG_DQN_REPLAY            // `make dqnreplay` (libevg_dqnreplay.so, with EVG_DQN, EVG_DQN_GRAD and EVG_DQN_LEARN): ... plus ...
+#include "dqn_replay_kernels.inc"   // that family's replay memory of raw observations: record, count, draw and the gather of optimize_model's batch
+#endif
 
 // ---------------------------------------------------------------------------------------------
 // launchers

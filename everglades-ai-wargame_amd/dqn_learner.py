@@ -5,6 +5,7 @@ libevg_dqnlearn.so).
     learner = env.dqn_learner(policy, target, lr=1e-4, gamma=0.99, mode="huber", clamp=1.0)
     loss = learner.step_on((state, action, next_state, reward, not_done))        # the policy's parameters updated in place; a 0-d device tensor
     loss, priorities = learner.step_on(batch, weights=w)
+    loss = learner.step(mem, 128, seed=t)                                        # the batch drawn from a DqnReplay (env.dqn_replay)
     learner.sync_target()                                                        # target.load_state_dict(policy.state_dict())
 
 What a step computes is agents/DQN/DQNAgent.py:220-290 (mode "huber": gather of the row's seven unravelled actions against target_net(next).topk(7)
@@ -172,6 +173,23 @@ class DqnFamilyLearner(object):
         ts = self.backward(state, b["q_pred"], b["gq"], b["grad_ws"])
         self.adam_step(ts)
         return self._loss0 if weights is None else (self._loss0, b["priorities"])
+
+    def step(self, mem, batch_size, seed, beta=None):
+        """One optimize_model on `batch_size` transitions drawn from a DqnReplay (env.dqn_replay): mem.sample(batch_size, seed), then step_on with the
+        memory's not_done (prioritized_optimize_model's (1 - done) rule; a terminal record's next_state is zeros).  With a PrioritizedDqnReplay and a
+        `beta`: mem.sample(batch_size, seed, beta), step_on with its importance weights, then mem.update_priorities(handles, self.priorities) with the
+        TD head's own priorities (duplicate handles keep the largest); beta=None draws uniformly from it (uniform_sample).  -> loss.  After the first
+        call with a given batch size it allocates nothing, runs no torch op and does not synchronise; a captured step replays bit for bit when
+        mem.sample_calls is set back to the value it had."""
+        if beta is None:
+            uniform = getattr(mem, "uniform_sample", None)
+            return self.step_on((uniform or mem.sample)(batch_size, seed))
+        if not hasattr(mem, "update_priorities"):
+            raise ValueError("beta needs a prioritized memory (env.dqn_prioritized_replay)")
+        out = mem.sample(batch_size, seed, beta)
+        loss, priorities = self.step_on(out[:5], weights=out[5])
+        mem.update_priorities(out[6], priorities)
+        return loss
 
     # ------------------------------------------------------------------ the rest of an optimizer
     def sync_target(self):

@@ -623,6 +623,21 @@ class EvergladesVecEnv(object):
         from .dqn_learner import DqnFamilyLearner
         return DqnFamilyLearner(self, policy, target, **kw)
 
+    def dqn_replay(self, capacity_turns, shaping="reward_short_games", seat=0, episode_base=0):
+        """The agents/DQN family's replay memory of raw observations on the device for this env (everglades_amd.DqnReplay; include/evg_dqn_replay.h):
+        remember_game_state, SimpleMemory.ReplayMemory and optimize_model's batch.  `mem.slot_obs(t)` is the `out=` of observe_seat / step_vs and the
+        network's input, `mem.slot_actions(t)` the `out=` of dqn_get_action; record / sample / gather run without a host synchronisation, and
+        `learner.step(mem, B, seed)` of dqn_learner() is one training step from it."""
+        from .dqn_replay import DqnReplay
+        return DqnReplay(self, capacity_turns, shaping=shaping, seat=seat, episode_base=episode_base)
+
+    def dqn_prioritized_replay(self, capacity_turns, alpha=0.6, shaping="reward_short_games", seat=0, episode_base=0):
+        """dqn_replay() that also samples by priority (everglades_amd.PrioritizedDqnReplay: agents/DQN/PrioritizedMemory.py's sample and
+        update_priorities over the same ring): sample(batch, seed, beta) draws by priority ** alpha and returns importance weights and handles,
+        update_priorities(handles, priorities) hands the new priorities back; learner.step(mem, B, seed, beta=...) does both.  No host synchronisation."""
+        from .dqn_replay import PrioritizedDqnReplay
+        return PrioritizedDqnReplay(self, capacity_turns, alpha=alpha, shaping=shaping, seat=seat, episode_base=episode_base)
+
     def q_population(self, team0, team1=None, final_relu=None, max_rows=None, precision="fp32"):
         """Self-royale (everglades_amd.QPopulation; evg_population): two teams of Minimized Q networks, a member per env and seat drawn each episode --
         `pop(shared, swarm)` -> the q [N, 2, 12, 11] step_q() takes, `pop.end_of_turn()` behind the step.  team1=None plays team0 on both seats.

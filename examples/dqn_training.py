@@ -10,9 +10,13 @@ and ring of raw observations, plus DQNAgent.optimize_model (DQNAgent.py:218-282)
 -- with the policy forward either torch's own (the default) or, with --device-backward, DqnQNet.with_grad: the same values from one launch, whose
 backward() is the device's backward pass (include/evg_dqn_grad.h).  The TD head and Adam of this family are torch's in both.  With --device-learner
 the whole torch block is one learner.step_on(batch) of env.dqn_learner (include/evg_dqn_learn.h): both forwards, the top-7 TD head, the backward and
-Adam as a chain of launches; the ring and the index draw stay torch's.
+Adam as a chain of launches; the ring and the index draw stay torch's.  With --device-replay (which implies --device-learner) the ring, the draw
+and the gathers are the device memory env.dqn_replay (include/evg_dqn_replay.h): the step writes each observation straight into the ring, the network
+reads it there, mem.record() follows the step and learner.step(mem, batch, seed) is the training step -- no torch op between step_vs and the updated
+parameters.  --prioritized (with --device-replay) samples by priority instead: prioritized_optimize_model (DQNAgent.py:294-337) with the squared loss,
+the importance weights and the TD head's priorities handed back, all inside learner.step(mem, batch, seed, beta).
 
-    python examples/dqn_training.py [envs] [turns] [batch] [--device-backward | --device-learner]
+    python examples/dqn_training.py [envs] [turns] [batch] [--device-backward | --device-learner | --device-replay [--prioritized]]
 """
 import math
 import os
@@ -32,7 +36,8 @@ def make_net(dev):
     return torch.nn.Sequential(torch.nn.Linear(105, 528), torch.nn.ReLU(), torch.nn.Linear(528, 132), torch.nn.ReLU()).to(dev)     # QNetwork.forward
 
 
-def main(envs=4096, turns=300, batch=128, device_backward=False, opponent="random_actions", ring=8, device_learner=False):
+def main(envs=4096, turns=300, batch=128, device_backward=False, opponent="random_actions", ring=8, device_learner=False, device_replay=False, prioritized=False):
+    device_learner = device_learner or device_replay
     env = evg.EvergladesVecEnv(envs, seed=1, auto_reset=True)
     env.reset()
     dev = env.device
@@ -41,8 +46,13 @@ def main(envs=4096, turns=300, batch=128, device_backward=False, opponent="rando
     target.load_state_dict(policy.state_dict())
     optimizer = torch.optim.Adam(policy.parameters(), lr=LR)
     qnet, tnet = env.dqn_qnet(policy), env.dqn_qnet(target)
-    learner = env.dqn_learner(policy, target, lr=LR, gamma=GAMMA, mode="huber", clamp=1.0) if device_learner else None
+    if prioritized:
+        learner = env.dqn_learner(policy, target, lr=LR, gamma=GAMMA, mode="squared", clamp=None)       # prioritized_optimize_model has no clamp
+    else:
+        learner = env.dqn_learner(policy, target, lr=LR, gamma=GAMMA, mode="huber", clamp=1.0) if device_learner else None
     explored = torch.zeros(envs, dtype=torch.uint8, device=dev)
+    if device_replay:
+        return device_replay_loop(env, qnet, learner, policy, envs, turns, batch, opponent, ring, explored, prioritized)
     mem = dict(state=torch.zeros((ring, envs, 105), device=dev), action=torch.zeros((ring, envs, 7), dtype=torch.int64, device=dev),
                reward=torch.zeros((ring, envs), device=dev), next_state=torch.zeros((ring, envs, 105), device=dev))
     gen = torch.Generator(device=dev).manual_seed(2)
@@ -94,13 +104,50 @@ def main(envs=4096, turns=300, batch=128, device_backward=False, opponent="rando
     return finite
 
 
+PER_ALPHA, PER_BETA = 0.6, 0.4                                     # PrioritizedMemory's defaults
+
+
+def device_replay_loop(env, qnet, learner, policy, envs, turns, batch, opponent, ring, explored, prioritized):
+    """the same loop on the device memory: `ring` turns of all envs, reward_short_games as dqn_training.py:148"""
+    if prioritized:
+        mem = env.dqn_prioritized_replay(capacity_turns=ring, alpha=PER_ALPHA, shaping="reward_short_games", seat=0)
+    else:
+        mem = env.dqn_replay(capacity_turns=ring, shaping="reward_short_games", seat=0)
+    env.observe_seat(0, out=mem.slot_obs(0))
+    steps_done, losses = 0, []
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    for t in range(turns):
+        eps = EPS_END + (EPS_START - EPS_END) * math.exp(steps_done * -EPS_DECAY)
+        steps_done += 1
+        rows = env.dqn_get_action(qnet(mem.slot_obs(t)), eps, seat=0, out=mem.slot_actions(t), explored=explored)
+        env.step_vs(opponent, rows, seat=0, out=mem.slot_obs(t + 1))
+        mem.record()
+        loss = learner.step(mem, batch, seed=t, beta=PER_BETA if prioritized else None)
+        if t % TARGET_UPDATE == TARGET_UPDATE - 1:
+            learner.sync_target()
+        if t % 20 == 19:                                           # the only host reads of the loop
+            losses.append(float(loss))
+    torch.cuda.synchronize()
+    dt = time.perf_counter() - t0
+    mem.check()
+    finite = all(bool(torch.isfinite(p).all()) for p in policy.parameters()) and all(math.isfinite(v) for v in losses)
+    print("%d envs x %d turns of the agents/DQN training loop against %s, batch %d, %sdevice replay (DqnReplay + DqnFamilyLearner.step): %.1f us per turn, "
+          "loss %s, all finite: %s" % (envs, turns, opponent, batch, "prioritized " if prioritized else "", dt / turns * 1e6, " ".join("%.4f" % v for v in losses), finite))
+    env.close()
+    return finite
+
+
 if __name__ == "__main__":
     flags = [a for a in sys.argv[1:] if a.startswith("--")]
     a = [v for v in sys.argv[1:] if not v.startswith("--")]
-    if set(flags) - {"--device-backward", "--device-learner"}:
-        sys.exit("unknown option %s" % " ".join(sorted(set(flags) - {"--device-backward", "--device-learner"})))
-    if len(flags) > 1:
+    known = {"--device-backward", "--device-learner", "--device-replay", "--prioritized"}
+    if set(flags) - known:
+        sys.exit("unknown option %s" % " ".join(sorted(set(flags) - known)))
+    if "--device-backward" in flags and len(set(flags)) > 1:
         sys.exit("--device-backward and --device-learner exclude each other")
+    if "--prioritized" in flags and "--device-replay" not in flags:
+        sys.exit("--prioritized needs --device-replay")
     ok = main(int(a[0]) if len(a) > 0 else 4096, int(a[1]) if len(a) > 1 else 300, int(a[2]) if len(a) > 2 else 128, "--device-backward" in flags,
-              device_learner="--device-learner" in flags)
+              device_learner="--device-learner" in flags, device_replay="--device-replay" in flags, prioritized="--prioritized" in flags)
     sys.exit(0 if ok else 1)
